@@ -16,6 +16,14 @@ multi-camera ray batch, and one RCCL all-gather of the rendered tiles gives
 every rank the step's N frames (weak scaling: per-GPU work is fixed).  A ray-sample is one (ray,
 shading-slot) entry of the dense H*W*SR grid the reference materialises
 (SURVEY 8(d)); value = all ranks' ray-samples / max-over-ranks time.
+
+A plain run sets up, warms up, times the K steps and prints one JSON line with
+the value, ms_per_step and the figures taken from the timed steps themselves.
+--full adds what needs runs of its own (grid build, stages alone and their
+rooflines, CPU baseline, accuracy vs the oracle and vs fp32x3, the finetune
+step).  --dump-outputs DIR writes what the last timed step returned to its
+caller as DIR/<name>.npy (same arguments, same inputs, so two builds compare
+output for output).
 """
 from __future__ import annotations
 
@@ -82,7 +90,16 @@ def parse():
                          "where the 15-ms KNN beside the bucketed aggregate holds CU slots its small kernels wait "
                          "for (DESIGN.md section 14: c5 879 vs 960 Mray-samples/s)")
     ap.add_argument("--no-query-stream", action="store_true", help="same as --query-stream off")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline value does not need, each "
+                         "in runs of its own: the grid build, the stages alone and their rooflines, the CPU "
+                         "baseline, the accuracy against the oracle and against fp32x3, and the finetune step "
+                         "('train'); default: the timed steps and the figures taken from them only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of the rays, listed in DIR/rays.npy, "
+                         "where the arrays are large)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU only, no libpnr: the N-rank launcher, sharding, all-gather and timing with a "
                          "stand-in render (tests/test_bench_launch.py; PNR_DIST_BACKEND defaults to gloo)")
@@ -112,6 +129,8 @@ def parse():
     args.hw = args.H
     args.dtype = args.dtype or cfg["dtype"]
     args.cpu_rays = args.cpu_rays or (12000 if args.config == "headline" else 3000)
+    if args.dump_outputs:   # relative to where bench.py was called from (the launcher's ranks run in ROOT)
+        args.dump_outputs = os.path.abspath(os.path.join(os.environ.get("PNR_BENCH_CWD", ""), args.dump_outputs))
     return args
 
 
@@ -236,6 +255,32 @@ def psnr_db(a, b):
 
 
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all files of one dump together
+
+
+def dump_outputs(dirname, groups):
+    """--dump-outputs: groups = [(prefix, {name: tensor})]; the tensors of one
+    group share their first axis (rays).  Every tensor is written as float32 to
+    dirname/<prefix><name>.npy.  A group whose share of DUMP_BUDGET_BYTES does
+    not hold all its rows is written for a seeded sample of them (the same rows
+    for every run with the same arguments), the sorted row numbers as
+    dirname/<prefix>rays.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(groups), 1)
+    for prefix, arrays in groups:
+        arrays = {k: torch.as_tensor(v) for k, v in arrays.items()}
+        rows = max(int(t.shape[0]) if t.dim() else 1 for t in arrays.values())
+        row_bytes = sum(4 * max(t.numel() // max(int(t.shape[0]), 1), 1) if t.dim() else 4 for t in arrays.values())
+        keep = max(1, (share - 64 * 1024) // (row_bytes + 8))
+        sel = None
+        if rows > keep:
+            sel = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+            np.save(os.path.join(dirname, f"{prefix}rays.npy"), sel.astype(np.float64))
+        for name, t in arrays.items():
+            if sel is not None and t.dim() and int(t.shape[0]) == rows:
+                t = t.index_select(0, torch.from_numpy(sel).to(t.device))
+            np.save(os.path.join(dirname, f"{prefix}{name}.npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def executed_roofline(args, stage, launches, avg_agg_s):
@@ -461,6 +506,7 @@ def run_train(args, device):
             stats["pairs"] += c["n_pairs"]
             stats["valid"] += c["S_valid"]
             stats["filled"] += c["S_filled"]
+        return color, loss
 
     for i in range(args.warmup):
         step(i, False)
@@ -468,13 +514,17 @@ def run_train(args, device):
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        step(args.warmup + i, True)
+        last = step(args.warmup + i, True)
     t_issue = time.perf_counter() - t0   # host time to issue the steps (the GPU may still be working)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     t = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and last is not None:
+        # the last timed step's rendered batch and its loss (the weights it trained are the model's state)
+        dump_outputs(args.dump_outputs, [("", {"ray_color": last[0].detach(), "loss": last[1].detach().reshape(1)})])
     if world > 1:
         tt = torch.tensor([t], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -541,6 +591,7 @@ def launch_ranks(args) -> int:
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC only on this pool (RCCL)
     env["PNR_BENCH_LAUNCHER"] = "self"
+    env["PNR_BENCH_CWD"] = os.getcwd()
     # the ranks' stderr passes through live (progress); their stdout is captured for the line
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=None, text=True, env=env, cwd=ROOT)
     out, _ = p.communicate()
@@ -600,6 +651,7 @@ def run_dry(args):
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
+    frames = []
     for s in range(args.steps):
         frames, cis = one_step(args.warmup + s)
         ok &= all(torch.equal(f, shade(cams[c])) for f, c in zip(frames, cis))
@@ -613,6 +665,8 @@ def run_dry(args):
         per_rank = [float(t[0]) for t in tl]
         ok = all(float(t[1]) == 1.0 for t in tl)
     t_max = max(per_rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [(f"frame{i}_", {"ray_color": f}) for i, f in enumerate(frames)])
     if rank == 0:
         print(json.dumps({
             "metric": "dry run (no GPU): assembled stand-in frames per second", "value": round(world * args.steps / t_max, 3),
@@ -736,10 +790,10 @@ def main():
         ev_step = [] if timed else None
         if shard_world > 1 and not args.per_frame_calls:
             st, rd, cp, cr = step_batch(s)
-            color = model.render_rays(cp, cr, rd, opt.near_plane, opt.far_plane, bg,
-                                      force_grid=args.grid_rebuild, events=ev_step, sync=False,
-                                      ray_cam=st.ray_cam, query_stream=qstream)[0]
-            parts.append((st, color, rd.shape[0]))
+            res = model.render_rays(cp, cr, rd, opt.near_plane, opt.far_plane, bg,
+                                    force_grid=args.grid_rebuild, events=ev_step, sync=False,
+                                    ray_cam=st.ray_cam, query_stream=qstream)
+            parts.append((st, res[0], rd.shape[0], res))
         else:
             for f in range(shard_world):
                 frame = s * shard_world + f
@@ -747,10 +801,10 @@ def main():
                     frame = fshard.frame_of(s)   # whole frame s*N + rank
                 ci, rd, sh = my_rays(frame)
                 campos, camrot, _ = dev_cams[ci]
-                color = model.render_rays(campos, camrot, rd, opt.near_plane, opt.far_plane, bg,
-                                          force_grid=(f == 0 and args.grid_rebuild),
-                                          events=ev_step, reuse_p1=f > 0, sync=False, query_stream=qstream)[0]
-                parts.append((sh, color, rd.shape[0]))
+                res = model.render_rays(campos, camrot, rd, opt.near_plane, opt.far_plane, bg,
+                                        force_grid=(f == 0 and args.grid_rebuild),
+                                        events=ev_step, reuse_p1=f > 0, sync=False, query_stream=qstream)
+                parts.append((sh, res[0], rd.shape[0], res))
         if timed:
             clock_probe()
         return parts, ev_step, timed
@@ -762,7 +816,7 @@ def main():
         parts, ev_step, timed = st
         counts = model.finish(upto=len(parts))
         if timed:
-            for c, (_, _, nr) in zip(counts, parts):
+            for c, (_, _, nr, _) in zip(counts, parts):
                 stage["pairs"] += c["n_pairs"]
                 stage["valid"] += c["S_valid"]
                 stage["filled"] += c["S_filled"]
@@ -772,7 +826,7 @@ def main():
             stage["_ev"] = stage.get("_ev", []) + ev_step
             stage["_step_pairs"] = stage.get("_step_pairs", []) + [sum(c["n_pairs"] for c in counts)]
         frames = []
-        for sh, color, _ in parts:
+        for sh, color, _, _ in parts:
             if world > 1 and not args.no_gather:
                 # RCCL all-gather of the rendered rays (async: they travel over xGMI while
                 # the next step renders): tiles -> one all-gather assembles the step's N
@@ -805,12 +859,22 @@ def main():
     pend = issue(args.warmup, True)
     for s in range(1, args.steps + 1):
         nxt = issue(args.warmup + s, True) if s < args.steps else None   # queued before step s-1's sync
+        last_parts = pend[0]
         cur = complete(pend)
         finish(prev)   # step s-2's all-gather travelled over xGMI while steps s-1 and s rendered
         prev, pend = cur, nxt
-    finish(prev)       # the last step's frames are gathered inside the timed region
+    last_frames = finish(prev)   # the last step's frames are gathered inside the timed region
     torch.cuda.synchronize()
     t_local = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back: every render call's outputs and,
+        # with N > 1, the frames the all-gather assembled on this rank
+        names = ("ray_color", "opacity", "is_bg", "ray_mask")
+        groups = [("" if len(last_parts) == 1 else f"call{i}_", dict(zip(names, res)))
+                  for i, (_, _, _, res) in enumerate(last_parts)]
+        if world > 1 and not args.no_gather:
+            groups += [(f"frame{i}_", {"ray_color": f}) for i, f in enumerate(last_frames)]
+        dump_outputs(args.dump_outputs, groups)
     per_rank_s = [t_local]
     if dist:
         dist.barrier()
@@ -935,35 +999,36 @@ def main():
             r = np.array(agg_ms)
             out["per_step"]["aggregate_spread"] = {"min": round(float(r.min()), 3), "max": round(float(r.max()), 3),
                                                    "cv": round(float(r.std() / r.mean()), 4)}
-        # the voxel grid persists across frames (the points do not change); its
-        # build (bbox read + 8 kernels + scans) on its own line
-        out["grid_build"] = time_grid_build(model, opt)
-        per_stage = per
-        if "p1" in per and shard_world == 1:
-            # the timed steps ran P1 beside the query: their frames again, stages alone, for the stage rooflines
-            per_stage = isolated_stage_times(model, opt, [dev_cams[(args.warmup + i) % len(dev_cams)]
-                                                          for i in range(args.steps)], bg)
-            out["stages_ms_isolated"] = {k: [round(float(x), 3) for x in v] for k, v in per_stage.items()}
-        out["stage_rooflines"] = stage_rooflines(args, opt, model, stage, per_stage, launches, out["grid_build"])
-        acc = {}
-        if not args.no_cpu_baseline and world == 1:
-            try:
-                out["cpu_baseline"], sel, ref = cpu_baseline(args, opt, pts, feats, agg, cams[0], H, W)
-                acc.update(accuracy_vs_oracle(model, opt, dev_cams[0], bg, sel, ref))
-            except Exception as e:  # the baseline must never hide the GPU number
-                out["cpu_baseline"] = {"value": None, "error": repr(e)}
-        if world == 1 and args.dtype in ("fp32h2", "bf16"):
-            acc.update(accuracy_vs_x3(model, opt, dev_cams[0], bg, args.dtype))
-        out["accuracy"] = acc
-        if world == 1 and args.config == "headline" and not args.no_train_line:
-            # SURVEY config c3's finetune step on the same box, outside the timed region
-            # (the line `bench.py --mode train` prints, with its own roofline)
-            del model, agg
-            torch.cuda.empty_cache()
-            try:
-                out["train"] = train_summary(args, device)
-            except Exception as e:  # the render line must never be lost to the training extra
-                out["train"] = {"error": repr(e)}
+        if args.full:
+            # the voxel grid persists across frames (the points do not change); its
+            # build (bbox read + 8 kernels + scans) on its own line
+            out["grid_build"] = time_grid_build(model, opt)
+            per_stage = per
+            if "p1" in per and shard_world == 1:
+                # the timed steps ran P1 beside the query: their frames again, stages alone, for the stage rooflines
+                per_stage = isolated_stage_times(model, opt, [dev_cams[(args.warmup + i) % len(dev_cams)]
+                                                              for i in range(args.steps)], bg)
+                out["stages_ms_isolated"] = {k: [round(float(x), 3) for x in v] for k, v in per_stage.items()}
+            out["stage_rooflines"] = stage_rooflines(args, opt, model, stage, per_stage, launches, out["grid_build"])
+            acc = {}
+            if not args.no_cpu_baseline and world == 1:
+                try:
+                    out["cpu_baseline"], sel, ref = cpu_baseline(args, opt, pts, feats, agg, cams[0], H, W)
+                    acc.update(accuracy_vs_oracle(model, opt, dev_cams[0], bg, sel, ref))
+                except Exception as e:  # the baseline must never hide the GPU number
+                    out["cpu_baseline"] = {"value": None, "error": repr(e)}
+            if world == 1 and args.dtype in ("fp32h2", "bf16"):
+                acc.update(accuracy_vs_x3(model, opt, dev_cams[0], bg, args.dtype))
+            out["accuracy"] = acc
+            if world == 1 and args.config == "headline" and not args.no_train_line:
+                # SURVEY config c3's finetune step on the same box, outside the timed region
+                # (the line `bench.py --mode train` prints, with its own roofline)
+                del model, agg
+                torch.cuda.empty_cache()
+                try:
+                    out["train"] = train_summary(args, device)
+                except Exception as e:  # the render line must never be lost to the training extra
+                    out["train"] = {"error": repr(e)}
         print(json.dumps(out), flush=True)
     if dist:
         dist.barrier()
@@ -976,6 +1041,7 @@ def train_summary(args, device):
     import copy
     targs = copy.copy(args)
     targs.mode, targs.steps, targs.warmup, targs.dtype = "train", 20, 5, "fp32"
+    targs.dump_outputs = None
     line = run_train(targs, device)
     keep = ("value", "unit", "ms_per_step", "dtype", "arith", "roofline", "h2_fallbacks", "optimizer", "config",
             "counts_per_step", "gemm_tflops_per_s", "host_issue_ms_per_step", "host_phase_ms_per_step")

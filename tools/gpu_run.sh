@@ -14,7 +14,7 @@ for s in $STEPS; do
         > $O/t_gpu.log 2>&1 || { tail -40 $O/t_gpu.log; exit 1; }
       tail -3 $O/t_gpu.log ;;
     bench)
-      timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+      timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
       cut -c1-600 $O/bench.json ;;
     gridprof)   # grid build kernel split, headline and c5 (GCONFIGS)
       for c in ${GCONFIGS:-headline c5}; do
@@ -51,13 +51,13 @@ for s in $STEPS; do
       done; done
       cat $O/adam.jsonl ;;
     launch)   # bench.py --gpus 2 self-launch rehearsal: two ranks on the box's one GPU over gloo
-      PNR_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 5 --warmup 2 > $O/launch2.json \
+      PNR_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --steps 5 --warmup 2 > $O/launch2.json \
         2> $O/launch2.err || { tail -20 $O/launch2.err; exit 1; }
       cut -c1-700 $O/launch2.json ;;
     c4|c5)
-      timeout -k 10 600 python bench.py --config $s --steps 5 --warmup 2 > $O/bench_$s.json 2> $O/bench_$s.err \
+      timeout -k 10 600 python bench.py --full --config $s --steps 5 --warmup 2 > $O/bench_$s.json 2> $O/bench_$s.err \
         || { tail -20 $O/bench_$s.err; exit 1; }
-      timeout -k 10 600 python bench.py --config $s --steps 3 --warmup 1 --emulate-world 8 --no-cpu-baseline \
+      timeout -k 10 600 python bench.py --full --config $s --steps 3 --warmup 1 --emulate-world 8 --no-cpu-baseline \
         > $O/bench_${s}_ew8.json 2> $O/bench_${s}_ew8.err || { tail -20 $O/bench_${s}_ew8.err; exit 1; }
       cut -c1-400 $O/bench_$s.json ;;
     nr)
@@ -128,6 +128,6 @@ for s in $STEPS; do
       bash tools/prof_bench.sh $(basename $O)/bp || { tail -20 $O/bp/*.log; exit 1; } ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- \
-        python bench.py --no-cpu-baseline > $O/stats.log 2>&1 || { tail -20 $O/stats.log; exit 1; } ;;
+        python bench.py --full --no-cpu-baseline > $O/stats.log 2>&1 || { tail -20 $O/stats.log; exit 1; } ;;
   esac
 done

@@ -18,8 +18,8 @@ case $DTYPE in
   *) MOPS=SQ_INSTS_VALU_MFMA_MOPS_BF16 ;;
 esac
 mkdir -p $O
-timeout -k 10 400 python bench.py --config $CONFIG --dtype $DTYPE $SW > $O/bench.json 2> $O/bench.err
-B="python bench.py --config $CONFIG --no-cpu-baseline --dtype $DTYPE $SW"
+timeout -k 10 400 python bench.py --full --config $CONFIG --dtype $DTYPE $SW > $O/bench.json 2> $O/bench.err
+B="python bench.py --full --config $CONFIG --no-cpu-baseline --dtype $DTYPE $SW"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- $B > $O/stats.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- $B > $O/fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o run -- $B > $O/write.log 2>&1
