@@ -44,6 +44,9 @@
  *                           color_branch Linear(128,3) + raw2out_color
  *                           models/aggregators/point_aggregators.py:343, 269-273, 637-638
  *                           (radiance_render [..., 1:4], diff_render_func.py:48-50)
+ *   pnr_probe            <- the opt.prob == 1 outputs of NeuralPointsRayMarching.forward
+ *                           that probe_hole grows points from
+ *                           models/neural_points_volumetric_model_ori.py:351-372
  */
 #ifndef PNR_H_
 #define PNR_H_
@@ -57,7 +60,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 23
+#define PNR_ABI_VERSION 24
 
 enum {
   PNR_OK = 0,
@@ -851,6 +854,24 @@ int pnr_weighted_colsum(const float* w, const float* x, int64_t R, int32_t C, fl
 int pnr_march_aux(const pnr_rays* rays, const pnr_query_params* q, const pnr_query_bufs* b,
                   const float* xyz, const float* opacity, int64_t rows_max, float* weight,
                   float* blend_weight, void* stream);
+
+/* The point-growing probe NeuralPointsRayMarching.forward adds with opt.prob == 1
+ * (neural_points_volumetric_model_ori.py:351-372; read by probe_hole,
+ * run/train_ft.py:473-515), from pnr_query's buffers, the point tables and
+ * pnr_composite_fwd's opacity[R,SR], in full ray order (ABI 24).  Per ray with
+ * ray_vcnt > 0: s* = argmax_s opacity[r,s] (the lowest slot among equal maxima),
+ * max_opacity[R] = opacity[r,s*], max_loc_w[R,3] = sample_loc_w[r,s*] (0 for an
+ * unfilled slot), far_dist[R] = min_k |xyz[max(pidx[r,s*,k], 0)] - max_loc_w|
+ * (empty slots gather point 0, neural_points.py:790), and avg_X = sum_k
+ * X[max(pidx, 0)] * weight_k * clamp(conf[max(pidx, 0)], 1e-4, 1) with
+ * pnr_march_aux's weight, X = color [R,3], dir [R,3], conf [R] (each NULL = not
+ * wanted; its table must be present) and the embedding [R,32] (pts->emb_bf16
+ * when set, else pts->emb).  Rows of the other rays are zeros.  K <= 16,
+ * SR <= 128.  One launch, no host sync, no allocation. */
+int pnr_probe(const pnr_rays* rays, const pnr_query_params* q, const pnr_query_bufs* b,
+              const pnr_points* pts, const float* opacity, float* max_opacity, float* max_loc_w,
+              float* far_dist, float* avg_color, float* avg_dir, float* avg_conf, float* avg_emb,
+              void* stream);
 
 /* -------------------------------------------------------- 2-D neural renderer
  * NeuralRenderer(input_dim=128) (models/neural_render/neural_renderer.py:24-104,

@@ -198,6 +198,10 @@ def _counts_dict(c):
 # pnr_aggregate_fwd_h2).  bf16: bf16 operands (config c5).
 PRECISIONS = ("fp32", "fp32x3", "fp32h2", "bf16")
 
+# forward's extra outputs with opt.prob == 1, in pnr_probe's argument order
+PROBE_KEYS = ("ray_max_shading_opacity", "ray_max_sample_loc_w", "ray_max_far_dist", "shading_avg_color",
+              "shading_avg_dir", "shading_avg_conf", "shading_avg_embedding")
+
 
 class _ZeroOneConfLoss(torch.autograd.Function):
     """NeuralPointsRayMarching.zero_one_conf_loss on libpnr: the per-point entry
@@ -988,6 +992,56 @@ class NeuralPointsRayMarching(nn.Module):
         cnt = bufs.read_counts()
         return self._march_aux(rays, qp, bufs, raydir.shape[0], cnt["R_valid"], xyz, opacity)
 
+    @torch.no_grad()
+    def probe_maps(self, campos, camrot, raydir, near, far, opacity):
+        """The seven opt.prob == 1 outputs of the reference's forward
+        (neural_points_volumetric_model_ori.py:351-372; PROBE_KEYS) for an
+        evaluation render, in full ray order: the batch's query again (like
+        eval_aux, chunk_rays at a time), then one pnr_probe launch per chunk on
+        the rendered opacity [R,SR] -- no compaction, no [R'',SR,K,*] tensors, no
+        host read.  Shapes [1,R,1] / [1,R,3] / [1,R,32]; None for an absent
+        point table; rows of rays without a neighbour are zeros."""
+        np_ = self.neural_points
+        raydir = raydir.reshape(-1, 3).float().contiguous()
+        dev = raydir.device
+        R, SR = raydir.shape[0], self.opt.SR
+        from .querier import camera_tables
+        cp, cr = camera_tables(campos, camrot, None)
+        xyz = np_.xyz.detach().contiguous()
+        pts, _keep = np_.tables(cp, cr, bf16=True)
+        op = opacity.detach().reshape(R, SR).float().contiguous()
+
+        def buf(c, have=True):
+            return torch.empty((1, R, c), dtype=torch.float32, device=dev) if have else None
+
+        out = dict(ray_max_shading_opacity=buf(1), ray_max_sample_loc_w=buf(3), ray_max_far_dist=buf(1),
+                   shading_avg_color=buf(3, np_.points_color is not None),
+                   shading_avg_dir=buf(3, np_.points_dir is not None),
+                   shading_avg_conf=buf(1, np_.points_conf is not None), shading_avg_embedding=buf(32))
+        chunk = max(1, self.chunk_rays or R)
+        bufs = None
+        for c0 in range(0, R, chunk):
+            c1 = min(c0 + chunk, R)
+            bufs, hp, rays, qp = np_.querier.run(xyz, raydir[c0:c1], cp, cr, near, far, bufs=bufs)
+            L.check(L.lib().pnr_probe(L.ctypes.byref(rays), L.ctypes.byref(qp), L.ctypes.byref(bufs.c),
+                                      L.ctypes.byref(pts), L.ptr(op[c0:c1]),
+                                      *(L.ptr(None if out[k] is None else out[k][0, c0:c1]) for k in PROBE_KEYS),
+                                      L.stream_ptr(dev)), "pnr_probe")
+        return out
+
+    def probe_rays(self, campos, camrot, raydir, near, far, bg_color):
+        """render_rays plus probe_maps for a ray batch [R,3] of any size
+        (chunk_rays at a time), for callers that do not go through forward:
+        dict of coarse_raycolor [1,R,C], coarse_point_opacity [1,R,SR],
+        coarse_is_background [1,R,1], ray_mask [1,R] and the PROBE_KEYS maps."""
+        raydir = raydir.reshape(-1, 3)
+        color, opacity, is_bg, ray_mask = self.render_rays(campos, camrot, raydir, near, far, bg_color)
+        R = raydir.shape[0]
+        out = dict(coarse_raycolor=color.view(1, R, -1), coarse_point_opacity=opacity.view(1, R, -1),
+                   coarse_is_background=is_bg.view(1, R, 1), ray_mask=ray_mask.view(1, R))
+        out.update(self.probe_maps(campos, camrot, raydir, near, far, opacity))
+        return out
+
     def zero_one_conf_loss(self, zero_epsilon: float = 1e-3):
         """zero_one_loss(conf_coefficient) of the last render_rays_train, computed
         per point: every entry of conf_coefficient is a function of one point's
@@ -1025,6 +1079,10 @@ class NeuralPointsRayMarching(nn.Module):
         # differentiable path; evaluation / no_grad: the fused forward
         train = torch.is_grad_enabled() and self.training and (
             any(p.requires_grad for p in self.parameters()) or (torch.is_tensor(bg_color) and bg_color.requires_grad))
+        prob = getattr(self.opt, "prob", 0) == 1
+        if train and prob:
+            raise L.PnrError("opt.prob == 1 (the point-growing probe) is an evaluation render, as in the "
+                             "reference's probe_hole: call the module in eval() mode or under no_grad")
         if train:
             color, opacity, is_bg, ray_mask = self.render_rays_train(campos, camrotc2w, raydir.reshape(-1, 3),
                                                                      near_v, far_v, bg_color)
@@ -1044,6 +1102,8 @@ class NeuralPointsRayMarching(nn.Module):
             out["weight"] = aux["weight"]
             out["blend_weight"] = aux["blend_weight"]
             out["conf_coefficient"] = aux["conf_coefficient"]
+        if prob and R > 0:   # neural_points_volumetric_model_ori.py:351-372
+            out.update(self.probe_maps(campos, camrotc2w, raydir.reshape(-1, 3), near_v, far_v, opacity))
         if self.neural_render_2d is not None:
             img_h = int(h.item()) if torch.is_tensor(h) else int(h)
             img_w = int(w.item()) if torch.is_tensor(w) else int(w)
