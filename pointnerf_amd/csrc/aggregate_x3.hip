@@ -6,7 +6,14 @@
 //     products per 16-k step on v_mfma_f32_32x32x16_bf16 (split2);
 //   * k_pairs_h2 (pnr_aggregate_fwd_h2): 2-way f16 split with a 2^11-scaled low
 //     half, three products on v_mfma_f32_32x32x16_f16 (splith) -- half the
-//     MFMA work, two activation planes instead of three.
+//     MFMA work, two activation planes instead of three.  The inference
+//     kernel (and k_point_pre_h2) keeps two accumulator sets per layer,
+//     main += Wh.Xh and corr += Wl.Xh + Wh.Xl, and folds 2048 main + corr once
+//     where the accumulators are consumed (`layer`'s ACC2), so the MFMA stream
+//     carries nothing but MFMAs and loads; the training kernel and
+//     k_color_h2, which have no registers for a second set, sum the three
+//     products in one set with Ws = 2^11 Wh made in registers
+//     (4 v_pk_mul_f16 per neuron tile and k-step, in the MFMA gaps).
 // Both are one kernel body templated on H (false: bf16 x3, true: f16 h2).
 //
 // Producer / consumer workgroup (one 8-wave workgroup per CU):
@@ -158,9 +165,19 @@ __device__ __forceinline__ void prime(WRing<H>& w, __amdgpu_buffer_rsrc_t rs, in
 // (plane stride pstride bytes, 64 pairs per 8-row group).  Weights kWD steps
 // ahead in the ring (slot d: steps = d mod kWD), B one step ahead.  NTK: neuron
 // tiles per k-step in the pack (256 outputs: 8, the colour branch: 4).
-template <bool H, int NTK = 8>
-__device__ __forceinline__ void layer(f32x16 (&acc)[4], WRing<H>& w, __amdgpu_buffer_rsrc_t rs, int voff,
-                                      const char* planes, int pstride, int nsteps, int lane) {
+// ACC2 (h2 only): two accumulator sets, acc += Wh.Xh and corr += Wl.Xh + Wh.Xl,
+// so no 2^11-scaled copy of Wh is made; the layer output is
+// 2048 scale (acc + 2^-11 corr) = scale (2048 acc + corr), folded by the caller
+// where the accumulators are consumed (fold2, store_act).  corr always starts
+// at 0 and acc, with ZACC, too: the first k-step is peeled and its MFMAs take
+// the constant 0 as C, so neither set is zeroed with moves (corr's / acc's
+// contents on entry are ignored).  Without ACC2 corr is unused and acc holds
+// 2048 Wh.Xh + Wl.Xh + Wh.Xl.
+template <bool H, int NTK = 8, bool ACC2 = false, bool ZACC = false>
+__device__ __forceinline__ void layer(f32x16 (&acc)[4], f32x16 (&corr)[4], WRing<H>& w, __amdgpu_buffer_rsrc_t rs,
+                                      int voff, const char* planes, int pstride, int nsteps, int lane) {
+  static_assert(ACC2 || !ZACC, "zero-start accumulators: with two accumulator sets only");
+  static_assert(H || !ACC2, "two accumulator sets: the f16 split only");
   constexpr int NPL = XL<H>::NPL, NPW = XL<H>::NPW, kWD = WRing<H>::kWD;
   const int c = lane & 31, h = lane >> 5;
   const char* base = planes + (h * kXT + c) * 16;
@@ -183,8 +200,14 @@ __device__ __forceinline__ void layer(f32x16 (&acc)[4], WRing<H>& w, __amdgpu_bu
   // its last MFMA of this step, so the loads sit in MFMA gaps instead of in
   // bursts; sched_barrier(0) pins the order (hipcc would otherwise sink the
   // LDS reads next to their uses and merge the waits).
-  auto mm = [&](int pt, const uint4& av0, const uint4& av1, const uint4& bv) {
-    if constexpr (H) {
+  // to_corr / zc (C = 0) are literals at every call: resolved when inlined
+  auto mm = [&](int pt, const uint4& av0, const uint4& av1, const uint4& bv, bool to_corr = false, bool zc = false) {
+    if constexpr (ACC2) {
+      f32x16 (&d)[4] = to_corr ? corr : acc;
+      const f32x16 z = {0.f};
+      d[2 * pt] = mfma_f16(av0, bv, zc ? z : d[2 * pt]);
+      d[2 * pt + 1] = mfma_f16(av1, bv, zc ? z : d[2 * pt + 1]);
+    } else if constexpr (H) {
       acc[2 * pt] = mfma_f16(av0, bv, acc[2 * pt]);
       acc[2 * pt + 1] = mfma_f16(av1, bv, acc[2 * pt + 1]);
     } else {
@@ -205,28 +228,30 @@ __device__ __forceinline__ void layer(f32x16 (&acc)[4], WRing<H>& w, __amdgpu_bu
   // h2 step per half: Ws.Xh, Wl.Xh, Wh.Xl (Ws = 2^11 Wh, made in registers)
   // Ws = 2^11 Wh of the NEXT step is made in the middle of this one (scl), so
   // the v_pk_mul_f16 results are never waited on by the MFMA right after them.
+  // ACC2: Wh.Xh into acc, the other two into corr; no Ws, nothing but the
+  // loads in the MFMA gaps.
   uint4 scl[2];
   auto scale_next = [&](const uint4 (&an)[2][NPW], int T) {   // one tile per MFMA gap (4 v_pk_mul_f16)
-    scl[T] = f16x8_scale2048(an[T][0]);
+    if constexpr (!ACC2) scl[T] = f16x8_scale2048(an[T][0]);
   };
   if constexpr (H) {
     scale_next(w.a[0], 0);
     scale_next(w.a[0], 1);
   }
-  auto step_h = [&](uint4 (&a)[2][NPW], const uint4 (&an)[2][NPW], int t, int bs) {
+  auto step_h = [&](uint4 (&a)[2][NPW], const uint4 (&an)[2][NPW], int t, int bs, bool first = false) {
     const int tn = t + BD < nsteps ? t + BD : nsteps - 1;
-    const uint4 s0 = scl[0], s1 = scl[1];
+    const uint4 s0 = ACC2 ? a[0][0] : scl[0], s1 = ACC2 ? a[1][0] : scl[1];
 #pragma unroll
     for (int pt = 0; pt < 2; ++pt) {
-      mm(pt, s0, s1, b[bs][pt][0]);                                // Ws.Xh
+      mm(pt, s0, s1, b[bs][pt][0], false, first && ZACC);          // Ws.Xh (ACC2: Wh.Xh)
       __builtin_amdgcn_sched_barrier(0);
-      mm(pt, a[0][1], a[1][1], b[bs][pt][0]);                      // Wl.Xh
+      mm(pt, a[0][1], a[1][1], b[bs][pt][0], true, first);         // Wl.Xh
       __builtin_amdgcn_sched_barrier(0);
       if (pt == 1) wl(a, 1, t + kWD);
       if (pt == 0) scale_next(an, 0);
       bl(bs, tn, pt, 0);
       __builtin_amdgcn_sched_barrier(0);
-      mm(pt, a[0][0], a[1][0], b[bs][pt][1]);                      // Wh.Xl
+      mm(pt, a[0][0], a[1][0], b[bs][pt][1], true);                // Wh.Xl
       __builtin_amdgcn_sched_barrier(0);
       bl(bs, tn, pt, 1);
       if (pt == 0) scale_next(an, 1);
@@ -268,16 +293,28 @@ __device__ __forceinline__ void layer(f32x16 (&acc)[4], WRing<H>& w, __amdgpu_bu
   };
   // unrolled by U = lcm(kWD, BD) so the weight and B slots are compile-time
   constexpr int U = (BD == 2 && kWD % 2) ? 2 * kWD : kWD;
-  int t = 0;
+  constexpr int P = ACC2 ? 1 : 0;   // ACC2: step 0 peeled (C = 0), the slots of the rest shifted by one
+  if constexpr (ACC2) step_h(w.a[0], w.a[1 % kWD], 0, 0, true);
+  int t = P;
 #pragma unroll 1
   for (; t + U <= nsteps; t += U) {
 #pragma unroll
-    for (int d = 0; d < U; ++d) step(w.a[d % kWD], w.a[(d + 1) % kWD], t + d, d % BD);
+    for (int d = 0; d < U; ++d) step(w.a[(d + P) % kWD], w.a[(d + P + 1) % kWD], t + d, (d + P) % BD);
   }
 #pragma unroll
   for (int d = 0; d < U - 1; ++d)   // the ring then holds padding; prime() refills it
-    if (t + d < nsteps) step(w.a[d % kWD], w.a[(d + 1) % kWD], t + d, d % BD);
+    if (t + d < nsteps) step(w.a[(d + P) % kWD], w.a[(d + P + 1) % kWD], t + d, (d + P) % BD);
 }
+
+template <bool H, int NTK = 8>
+__device__ __forceinline__ void layer(f32x16 (&acc)[4], WRing<H>& w, __amdgpu_buffer_rsrc_t rs, int voff,
+                                      const char* planes, int pstride, int nsteps, int lane) {
+  layer<H, NTK, false>(acc, acc, w, rs, voff, planes, pstride, nsteps, lane);
+}
+
+// ACC2 fold of one accumulator value: 2048 main + corr (times the layer's
+// scale[] = the layer output; what a single-accumulator layer leaves in acc)
+__device__ __forceinline__ float fold2(float main, float corr) { return fmaf(main, 2048.f, corr); }
 
 // (x0, x1) -> f16 split of y = lrelu(x mul) (splith's planes: hi = f16(y),
 // lo = f16((y - hi) 2^11), bit-identical), from Y = 2^11 y = max(x k, x ks)
@@ -301,9 +338,11 @@ __device__ __forceinline__ void lrelu_splith(float x0, float x1, float k, float 
 // ds_write_b64 per plane and quad.  (h2: an activation beyond the f16 range
 // becomes an infinite high half; the launch detects it from its non-finite
 // outputs, see the range flag, instead of testing every activation.)
-template <bool H>
-__device__ __forceinline__ void store_act(const f32x16 (&acc)[4], char* planes, float s, float mul, int lane,
-                                          int T0, int pstride = kPlaneX) {
+// ACC2: the layer's two accumulator sets are folded here (one packed fma per
+// pair of values, outside the MFMA stream).
+template <bool H, bool ACC2 = false>
+__device__ __forceinline__ void store_act(const f32x16 (&acc)[4], const f32x16 (&corr)[4], char* planes, float s,
+                                          float mul, int lane, int T0, int pstride = kPlaneX) {
   const int c = lane & 31, h = lane >> 5;
   if constexpr (H) {
     const float k = 2048.f * mul, ks = k * s;   // exact: mul is a power of two
@@ -313,10 +352,13 @@ __device__ __forceinline__ void store_act(const f32x16 (&acc)[4], char* planes, 
       for (int T = 0; T < 2; ++T)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const f32x16& v = acc[2 * pt + T];
+          float v[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            v[i] = ACC2 ? fold2(acc[2 * pt + T][4 * q + i], corr[2 * pt + T][4 * q + i]) : acc[2 * pt + T][4 * q + i];
           unsigned a0, a1, b0, b1;
-          lrelu_splith(v[4 * q], v[4 * q + 1], k, ks, a0, a1);
-          lrelu_splith(v[4 * q + 2], v[4 * q + 3], k, ks, b0, b1);
+          lrelu_splith(v[0], v[1], k, ks, a0, a1);
+          lrelu_splith(v[2], v[3], k, ks, b0, b1);
           char* d = planes + ((4 * (T0 + T) + q) * kXT + 32 * pt + c) * 16 + 8 * h;
           *reinterpret_cast<uint2*>(d) = make_uint2(a0, b0);
           *reinterpret_cast<uint2*>(d + pstride) = make_uint2(a1, b1);
@@ -341,9 +383,16 @@ __device__ __forceinline__ void store_act(const f32x16 (&acc)[4], char* planes, 
       }
 }
 
+template <bool H>
+__device__ __forceinline__ void store_act(const f32x16 (&acc)[4], char* planes, float s, float mul, int lane,
+                                          int T0, int pstride = kPlaneX) {
+  store_act<H, false>(acc, acc, planes, s, mul, lane, T0, pstride);
+}
+
 // h2: block1.2 / block3.2 biases start the accumulators (acc = b / scale,
 // exact: the scale is a power of two) instead of riding in the GEMM as an
-// extra input row, so those layers take 16 k-steps instead of 17.
+// extra input row, so those layers take 16 k-steps instead of 17.  (ACC2
+// layers: inv_scale = 1 / (2048 scale).)
 template <bool H>
 __device__ __forceinline__ void acc_init(f32x16 (&acc)[4], const float* bias, float inv_scale, int lane, int T0) {
   if constexpr (H) {
@@ -671,8 +720,19 @@ __device__ __forceinline__ void consumer_loop(const X3Args& A, char* lds, int wi
                                r4 = rsrc(A.wx.pack[3]);
   // layer output factors (h2: 2^(s-11) of the pre-scaled f16 packs; x3: 1, unused)
   const float sc1 = A.wx.scale[0], sc2 = A.wx.scale[1], sc3 = A.wx.scale[2], sc4 = A.wx.scale[3];
+  // two accumulator sets (layer's ACC2) on the h2 inference kernel; the training
+  // kernel keeps one (the second set makes it spill)
+  constexpr bool A2 = H && !TR;
+  const float in2 = A2 ? 0x1p-11f : 1.f;   // acc_init: bias / (2048 scale)
   WRing<H> wr;
   f32x16 acc[4];
+  f32x16 corr[4];   // A2 only
+  auto zero_acc = [&]() {   // (A2: the layer starts both sets from the constant 0)
+    if constexpr (!A2) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[i] = (f32x16){0.f};
+    }
+  };
   prime<H>(wr, r1, voff);
   X3_SYNC();   // S0: the first tile's PE planes, extras and weights are in LDS
   const int* TQ = reinterpret_cast<const int*>(lds + L::OffTq);
@@ -680,9 +740,8 @@ __device__ __forceinline__ void consumer_loop(const X3Args& A, char* lds, int wi
   for (int64_t tile = first_tile(ntiles); tile < ntiles; tile = TQ[(it + 1) & 3], ++it) {
     const int buf = it & 1;
     // ------------------------------------------------------------ block1.0 = P1 + W1[:, 224:] . PE_5
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = (f32x16){0.f};
-    layer<H>(acc, wr, r1, voff, PE, kPlaneP, 4, lane);
+    zero_acc();
+    layer<H, 8, A2, A2>(acc, corr, wr, r1, voff, PE, kPlaneP, 4, lane);
     prime<H>(wr, r2, voff);
     X3_SYNC();   // S1: P1 parked, PE planes consumed
 #pragma unroll
@@ -693,7 +752,13 @@ __device__ __forceinline__ void consumer_loop(const X3Args& A, char* lds, int wi
         for (int q = 0; q < 4; ++q) {
           const float4 v4 = *reinterpret_cast<const float4*>(P1L + (32 * pt + c) * kP1Pitch + 32 * (T0 + T) + 8 * q +
                                                              4 * h);
-          if constexpr (H) {
+          if constexpr (A2) {   // P1 + sc1 (2048 acc + corr), folded as two fmas
+            const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              acc[2 * pt + T][4 * q + i] =
+                  fmaf(acc[2 * pt + T][4 * q + i], 2048.f * sc1, fmaf(corr[2 * pt + T][4 * q + i], sc1, v[i]));
+          } else if constexpr (H) {
             acc[2 * pt + T][4 * q] = fmaf(acc[2 * pt + T][4 * q], sc1, v4.x);
             acc[2 * pt + T][4 * q + 1] = fmaf(acc[2 * pt + T][4 * q + 1], sc1, v4.y);
             acc[2 * pt + T][4 * q + 2] = fmaf(acc[2 * pt + T][4 * q + 2], sc1, v4.z);
@@ -716,13 +781,13 @@ __device__ __forceinline__ void consumer_loop(const X3Args& A, char* lds, int wi
         *reinterpret_cast<uint4*>(XP + pl * kPlaneX + (33 * kXT + lane) * 16) = make_uint4(0u, 0u, 0u, 0u);
       }
     }
-    acc_init<H>(acc, A.w.b2, 1.f / sc2, lane, T0);
+    acc_init<H>(acc, A.w.b2, in2 / sc2, lane, T0);
     X3_SYNC();   // S2
     // ------------------------------------------------------------ block1.2
-    layer<H>(acc, wr, r2, voff, XP, kPlaneX, kBiasSteps(H), lane);
+    layer<H, 8, A2>(acc, corr, wr, r2, voff, XP, kPlaneX, kBiasSteps(H), lane);
     prime<H>(wr, r3, voff);
     X3_SYNC();   // S3
-    store_act<H>(acc, XP, neg, sc2, lane, T0);
+    store_act<H, A2>(acc, corr, XP, neg, sc2, lane, T0);
     if constexpr (TR) save_act_train<H>(A, acc, A.sv.h2, 1, tile, n, neg, lane, T0, sc2);
     if (wid == 0) {   // block3.0 inputs 256..263: colour, R.dir - R.v, <R.dir, R.v>, bias
       const float* exL = reinterpret_cast<const float*>(lds + L::OffEx) + buf * 8 * kXT;
@@ -731,14 +796,13 @@ __device__ __forceinline__ void consumer_loop(const X3Args& A, char* lds, int wi
       for (int e = 0; e < 8; ++e) ex[e] = exL[e * kXT + lane];
       store_group<H>(XP, kPlaneX, 32, lane, ex);
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = (f32x16){0.f};
+    zero_acc();
     X3_SYNC();   // S4
     // ------------------------------------------------------------ block3.0
-    layer<H>(acc, wr, r3, voff, XP, kPlaneX, 17, lane);
+    layer<H, 8, A2, A2>(acc, corr, wr, r3, voff, XP, kPlaneX, 17, lane);
     prime<H>(wr, r4, voff);
     X3_SYNC();   // S5
-    store_act<H>(acc, XP, neg, sc3, lane, T0);
+    store_act<H, A2>(acc, corr, XP, neg, sc3, lane, T0);
     if constexpr (TR) save_act_train<H>(A, acc, A.sv.h3, 2, tile, n, neg, lane, T0, sc3);
     if (wid == 0 && !H) {
 #pragma unroll
@@ -746,15 +810,16 @@ __device__ __forceinline__ void consumer_loop(const X3Args& A, char* lds, int wi
         *reinterpret_cast<uint4*>(XP + pl * kPlaneX + (32 * kXT + lane) * 16) =
             make_uint4(pl == 0 ? L::kOne : 0u, 0u, 0u, 0u);
     }
-    acc_init<H>(acc, A.w.b4, 1.f / sc4, lane, T0);
+    acc_init<H>(acc, A.w.b4, in2 / sc4, lane, T0);
     X3_SYNC();   // S6
     // ------------------------------------------------------------ block3.2, alpha partials, K sums
-    layer<H>(acc, wr, r4, voff, XP, kPlaneX, kBiasSteps(H), lane);
+    layer<H, 8, A2>(acc, corr, wr, r4, voff, XP, kPlaneX, kBiasSteps(H), lane);
     prime<H>(wr, r1, voff);   // the next tile's block1.0
     if constexpr (H) {
       if constexpr (TR) save_act_train<H>(A, acc, A.sv.h4, 3, tile, n, neg, lane, T0, sc4);
       // block3.2 accumulators -> LDS [pair][row] for the producers' tail (next tile):
-      // one ds_write_b128 per accumulator quad, conflict-free at kP1Pitch
+      // one ds_write_b128 per accumulator quad, conflict-free at kP1Pitch (A2:
+      // parked folded, so the tail's factor stays scale[3])
       float* H4 = reinterpret_cast<float*>(lds + L::OffH4);
 #pragma unroll
       for (int pt = 0; pt < 2; ++pt)
@@ -762,9 +827,12 @@ __device__ __forceinline__ void consumer_loop(const X3Args& A, char* lds, int wi
         for (int T = 0; T < 2; ++T)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const f32x16& v = acc[2 * pt + T];
+            float v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              v[i] = A2 ? fold2(acc[2 * pt + T][4 * q + i], corr[2 * pt + T][4 * q + i]) : acc[2 * pt + T][4 * q + i];
             *reinterpret_cast<float4*>(H4 + (32 * pt + c) * kP1Pitch + 32 * (T0 + T) + 8 * q + 4 * h) =
-                make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+                make_float4(v[0], v[1], v[2], v[3]);
           }
     } else {
       if constexpr (TR) save_act_train<H>(A, acc, A.sv.h4, 3, tile, n, neg, lane, T0, 1.f);
@@ -1289,7 +1357,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   const __amdgpu_buffer_rsrc_t rw = rsrc(A.pack);
   float chk = 0.f;   // 0 * outputs: NaN once one is not finite (an input beyond the f16 range)
   WRing<true> wr;
-  f32x16 acc[4];
+  f32x16 acc[4], corr[4];
   prime<true>(wr, rw, voff);
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     // thread (point lane, channel block wid): emb channels 8 wid .. 8 wid + 7 and their PE
@@ -1338,9 +1406,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       }
     }
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = (f32x16){0.f};
-    layer<true>(acc, wr, rw, voff, lds, kP1Plane, 15, lane);
+    layer<true, 8, true, true>(acc, corr, wr, rw, voff, lds, kP1Plane, 15, lane);
     prime<true>(wr, rw, voff);   // the next tile
 #pragma unroll
     for (int pt = 0; pt < 2; ++pt) {
@@ -1349,9 +1415,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       for (int T = 0; T < 2; ++T)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const f32x16& v = acc[2 * pt + T];
-          const float4 o = make_float4(v[4 * q] * A.scale, v[4 * q + 1] * A.scale, v[4 * q + 2] * A.scale,
-                                       v[4 * q + 3] * A.scale);
+          const f32x16& m = acc[2 * pt + T];
+          const f32x16& r = corr[2 * pt + T];   // two accumulator sets: scale (2048 main + corr)
+          const float4 o = make_float4(fold2(m[4 * q], r[4 * q]) * A.scale, fold2(m[4 * q + 1], r[4 * q + 1]) * A.scale,
+                                       fold2(m[4 * q + 2], r[4 * q + 2]) * A.scale,
+                                       fold2(m[4 * q + 3], r[4 * q + 3]) * A.scale);
           chk = fmaf(0.f, (o.x + o.y) + (o.z + o.w), chk);
           if (prow < np)
             *reinterpret_cast<float4*>(A.p1 + prow * kHid + 32 * (T0 + T) + 8 * q + 4 * h) = o;
