@@ -80,6 +80,7 @@ struct XL {
 };
 
 constexpr int kProducerPrio = 3;   // producer wave priority (s_setprio): measured 0: 110.6, 2: 110.1, 3: 109.6 ms
+constexpr int kStoreWindowPrio = 0;   // k_pairs_h2 producer work beside an activation store: 0: 59.9, 3: 60.3 ms (1: as 3)
 
 typedef float f32x2n __attribute__((ext_vector_type(2)));
 typedef float f32x4n __attribute__((ext_vector_type(4)));
@@ -644,10 +645,10 @@ __device__ __forceinline__ void pe_planes(char* lds, int pw, int lane, const flo
 //   S1  C: acc += P1 (parked)   |
 //   S1b C: store act1, bias     |
 //   S2  C: block1.2             | P: gather(next)
-//   S3  C: store act2, extras   | P: fetch P1(next) (registers), PE planes part 1
-//   S4  C: block3.0             |
-//   S5  C: store act3, bias     | P: PE planes part 2
-//   S6  C: block3.2, K sums, alpha partials
+//   S3  C: store act2, extras   | P: fetch P1(next) (registers)
+//   S4  C: block3.0             | P: PE planes part 1 (k_pairs_h2: in S5..S6), h2: tail part 2
+//   S5  C: store act3, bias     | P: k_pairs_h2: PE planes part 1
+//   S6  C: block3.2, K sums, alpha partials | P: PE planes part 2
 //   S7
 // The consumers never wait on a producer phase shorter than the layer it
 // overlaps; the P1 rows travel during block3.0 / block3.2.
@@ -1021,6 +1022,9 @@ __device__ __forceinline__ void producer_tail(const X3Args& A, char* lds, int sl
 template <bool H, bool TR = false>
 __device__ __forceinline__ void producer_loop(const X3Args& A, char* lds, int pw, int lane) {
   using L = XL<H>;
+  // h2 inference only: producer work moved into an activation-store window (the
+  // x3 and the training kernels keep their schedule; not measured there)
+  constexpr bool SW = H && !TR;
   const int64_t n = eff_n(A.s);
   const int64_t ntiles = cdiv(n, kXTS);
   __builtin_amdgcn_s_setprio(kProducerPrio);   // producer issue priority over the MFMA stream
@@ -1066,12 +1070,20 @@ __device__ __forceinline__ void producer_loop(const X3Args& A, char* lds, int pw
     // the P1 rows travel during block3.0 / block3.2 (loads stay in flight across the barriers)
     p1e = fetch_p1(p1r, A, reinterpret_cast<const int*>(lds + L::OffPr) + nbuf * kXT, pw, lane);
     X3_SYNC();   // S4
-    pe_planes<H, 0, TR>(lds, pw, lane, dr6, &A, &g);   // during block3.0 (PE planes free since S1)
+    if constexpr (!SW) pe_planes<H, 0, TR>(lds, pw, lane, dr6, &A, &g);   // during block3.0 (PE planes free since S1)
     // (h2) during block3.0: the second half of the previous tile's tail (its
     // accumulators are overwritten after this tile's S6)
     if constexpr (H)
       if (it > 0) producer_tail<1, TR>(A, lds, (it + 2) % 3, prev, pw, lane, ts, chk);
     X3_SYNC();   // S5
+    // SW: PE part 1 beside the consumers' act3 store, which leaves half of the
+    // SIMD's issue slots unused, instead of beside block3.0's MFMA stream (the
+    // planes are read again only after S7; dr6 is the gather's of this iteration)
+    if constexpr (SW) {
+      __builtin_amdgcn_s_setprio(kStoreWindowPrio);   // the store's own VALU goes first
+      pe_planes<H, 0, TR>(lds, pw, lane, dr6, &A, &g);
+      __builtin_amdgcn_s_setprio(kProducerPrio);
+    }
     X3_SYNC();   // S6
     pe_planes<H, 1, TR>(lds, pw, lane, dr6, &A, &g);   // during block3.2
     X3_SYNC();   // S7
