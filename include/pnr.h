@@ -60,7 +60,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 24
+#define PNR_ABI_VERSION 25
 
 enum {
   PNR_OK = 0,
@@ -854,6 +854,50 @@ int pnr_weighted_colsum(const float* w, const float* x, int64_t R, int32_t C, fl
 int pnr_march_aux(const pnr_rays* rays, const pnr_query_params* q, const pnr_query_bufs* b,
                   const float* xyz, const float* opacity, int64_t rows_max, float* weight,
                   float* blend_weight, void* stream);
+
+/* ------------------------------------------------------- finetune objective
+ * The colour items of compute_losses (base_rendering_model.py:542-606) for one
+ * output tensor x[R,C] (row stride ldx floats) against gt[R,C] (row stride ldgt),
+ * all four kinds in one pass (ABI 25).  With S = sum over the kind's rays and
+ * channels of (x - gt)^2 and n its rays:
+ *   out[0]  every ray                          S / (R C)
+ *   out[1]  ray_masked_:       ray_mask > 0    S / (n C)
+ *   out[2]  ray_miss_:         ray_mask == 0   S / C   (MSELoss x n, :560)
+ *   out[3]  ray_depth_masked_: extra_mask > 0  S / (n C)   (extra_mask NULL: empty)
+ * An empty kind gives exactly 0 (the reference's ray_depth_masked_ gives NaN
+ * there).  counts[4] = (R, n_hit, n_miss, n_extra) as int64 on the device.  C <=
+ * 128.  scratch: pnr_color_loss_scratch_bytes bytes, 8-B aligned.  Sums in fp64
+ * over fixed per-block ranges, the block partials added in block order: bitwise
+ * repeatable.  Two launches, no host read.
+ * The backward (one launch): d_x[r,c] (row stride ldd) = 2 (x - gt) sum_k
+ * g_kind[k] coef_k(r), coef = 1 / (R C), 1 / (n_hit C), 1 / C, 1 / (n_extra C) for
+ * the kinds ray r belongs to (0 for an empty kind), from the forward's device
+ * counts and the device vector g_kind[4] = upstream gradient x item weight. */
+int pnr_color_loss_scratch_bytes(size_t* out);
+int pnr_color_loss_fwd(const float* x, int64_t ldx, const float* gt, int64_t ldgt, const int8_t* ray_mask,
+                       const uint8_t* extra_mask, int64_t R, int32_t C, float* out, int64_t* counts,
+                       void* scratch, size_t scratch_bytes, void* stream);
+int pnr_color_loss_bwd(const float* x, int64_t ldx, const float* gt, int64_t ldgt, const int8_t* ray_mask,
+                       const uint8_t* extra_mask, int64_t R, int32_t C, const int64_t* counts,
+                       const float* g_kind, float* d_x, int64_t ldd, void* stream);
+
+/* The sparse loss (base_rendering_model.py:652-662), sum(weight |1 - exp(-2 cc)|)
+ * / (sum(weight) + 1e-6), from pnr_query's buffers of R rays (ABI 25): weight is
+ * pnr_march_aux's normalised weight of every pair of the rays with a neighbour,
+ * cc = clamp(conf, 1e-4, 1) of the pair's point (conf NULL: cc = 1).  Computed per
+ * point: w_fix[N] receives W_p = the summed weight of the pairs gathering p, in
+ * 64-bit fixed point (2^38 per unit, integer atomics: order-free, so bitwise
+ * repeatable; R SR K <= 2^25), then out[0] = sum_p W_p f(cc_p) / (sum_p W_p + 1e-6)
+ * and state[0] = that denominator.  scratch: pnr_sparse_loss_scratch_bytes bytes;
+ * w_fix, state, scratch 8-B aligned.  No host read, no compaction.
+ * The backward (one launch): d_conf[p] = g[0] W_p f'(cc_p) / state[0], gradiant_clamp's
+ * straight-through gradient (no clamp mask); 0 for points without pairs. */
+int pnr_sparse_loss_scratch_bytes(size_t* out);
+int pnr_sparse_loss_fwd(const pnr_query_params* q, const pnr_query_bufs* b, int64_t R, const float* xyz,
+                        const float* conf, int64_t N, uint64_t* w_fix, float* out, double* state,
+                        void* scratch, size_t scratch_bytes, void* stream);
+int pnr_sparse_loss_bwd(const uint64_t* w_fix, const float* conf, int64_t N, const double* state, const float* g,
+                        float* d_conf, void* stream);
 
 /* The point-growing probe NeuralPointsRayMarching.forward adds with opt.prob == 1
  * (neural_points_volumetric_model_ori.py:351-372; read by probe_hole,

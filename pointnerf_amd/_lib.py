@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PNR_LIB", os.path.join(_HERE, "libpnr.so"))
 c_int, c_int8, c_int32, c_int64 = ctypes.c_int, ctypes.c_int8, ctypes.c_int32, ctypes.c_int64
 c_float, c_size_t, c_void_p = ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 PNR_OK, PNR_EINVAL, PNR_EOVERFLOW, PNR_EHIP, PNR_ENOMEM = 0, 1, 2, 3, 4
-ABI_VERSION = 24
+ABI_VERSION = 25
 FEAT_H_PITCH = 136   # PNR_FEAT_H_PITCH: uint16 per bf16 feature row (pnr_aggregate_fwd_bf16_hf)
 HEAD_BWD_BLOCKS = 512   # PNR_HEAD_BWD_BLOCKS (include/pnr.h)
 
@@ -276,6 +276,15 @@ SIGNATURES = {
     "pnr_weighted_colsum": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "pnr_march_aux": (c_int, [P(Rays), P(QueryParams), P(QueryBufs), c_void_p, c_void_p, c_int64, c_void_p,
                               c_void_p, c_void_p]),
+    "pnr_color_loss_scratch_bytes": (c_int, [P(c_size_t)]),
+    "pnr_color_loss_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32,
+                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnr_color_loss_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32,
+                                   c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "pnr_sparse_loss_scratch_bytes": (c_int, [P(c_size_t)]),
+    "pnr_sparse_loss_fwd": (c_int, [P(QueryParams), P(QueryBufs), c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnr_sparse_loss_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnr_probe": (c_int, [P(Rays), P(QueryParams), P(QueryBufs), P(Points), c_void_p, c_void_p, c_void_p, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnr_composite_fwd":(c_int, [P(Rays), P(QueryParams), P(QueryBufs), P(CompositeParams),

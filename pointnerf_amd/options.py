@@ -24,6 +24,9 @@ LEGO = dict(
     point_conf_mode="1", default_conf=0.15, raydist_mode_unit=1, near_plane=2.0, far_plane=6.0,
     which_render_func="radiance", which_blend_func="alpha", which_tonemap_func="off",
     sparse_loss_weight=0, zero_one_loss_items=["conf_coefficient"], prob=0,
+    # the objective (lego.sh:144-153; pointnerf_amd.losses.RenderLoss)
+    color_loss_items=["ray_masked_coarse_raycolor", "ray_miss_coarse_raycolor", "coarse_raycolor"],
+    color_loss_weights=[1.0, 0.0, 0.0], zero_one_loss_weights=[0.0001], zero_epsilon=1e-3,
     # point growing (lego.sh:136-142; pointnerf_amd.probe.probe_hole); prob is raised by probe_hole only
     prob_thresh=0.7, prob_mul=0.4, far_thresh=-1.0, prob_kernel_size=[3, 3, 3], prob_tiers=[100000],
     prob_num_step=20,

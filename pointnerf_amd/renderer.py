@@ -1057,6 +1057,28 @@ class NeuralPointsRayMarching(nn.Module):
         conf = self.neural_points.points_conf.reshape(-1)
         return _ZeroOneConfLoss.apply(conf, bufs, self.opt.SR, self.opt.K, float(zero_epsilon))
 
+    def sparse_conf_loss(self):
+        """The sparse loss (base_rendering_model.py:652-662) of the last
+        render_rays_train, sum(weight |1 - exp(-2 conf_coefficient)|) /
+        (sum(weight) + 1e-6), computed per point like zero_one_conf_loss: with
+        W_p the summed weight of the pairs that gather point p it equals
+        sum_p W_p f(cc_p) / (sum_p W_p + 1e-6), and d conf_p = g W_p f'(cc_p) /
+        (sum W + 1e-6) (gradiant_clamp's straight-through gradient).  The pair
+        weights are recomputed from the query buffers as pnr_march_aux writes
+        them (detached; empty slots weigh 0): no host read of R'', no
+        compaction, no [1, R'', SR, K] tensors.  Without a conf table
+        conf_coefficient is 1: a value without a gradient.  Bitwise repeatable
+        (losses._SparseConfLoss)."""
+        from .losses import _SparseConfLoss
+        bufs = self._train_conf_src
+        if bufs is None:
+            raise L.PnrError("sparse_conf_loss: no training render yet (call render_rays_train / forward in "
+                             "training mode first)")
+        qp = L.QueryParams()
+        qp.SR, qp.K = bufs.SR, bufs.K
+        np_ = self.neural_points
+        return _SparseConfLoss.apply(np_.points_conf, np_.xyz.detach().contiguous(), bufs, qp)
+
     @staticmethod
     def zero_one_loss(val, zero_epsilon: float = 1e-3):
         """base_rendering_model.py:630-641: mean(log(v) + log(1 - v)), v clamped
