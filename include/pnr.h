@@ -47,6 +47,9 @@
  *   pnr_probe            <- the opt.prob == 1 outputs of NeuralPointsRayMarching.forward
  *                           that probe_hole grows points from
  *                           models/neural_points_volumetric_model_ori.py:351-372
+ *   pnr_camera_rays,
+ *   pnr_ray_batch        <- the dataset item: pixel picks, get_dtu_raydir, ground truth, bg coin
+ *                           data/nerf_synth360_ft_dataset.py:546-635, data/data_utils.py:55-69
  */
 #ifndef PNR_H_
 #define PNR_H_
@@ -60,7 +63,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 25
+#define PNR_ABI_VERSION 26
 
 enum {
   PNR_OK = 0,
@@ -518,7 +521,12 @@ int pnr_aggregate_fwd_train_masked(const pnr_points* pts, const pnr_samples* s, 
  * of empty pairs are 0) and dpa[n_max*8]; accumulates (atomically, so the
  * caller zeroes them) d_p1[N,256] += dz1 per point (block1.0 point half; rows
  * are used_map[point] when pts->used is set, i.e. d_p1 is [n_used,256]),
- * d_color[N,3], d_dir[N,3], d_conf[N] (straight-through clamp gradient).
+ * d_color[N,3], d_dir[N,3].  d_conf (ABI 26; also in the _x3 / _h2 variants) is
+ * per PAIR: d_conf[n_max*8] receives each pair's term of the conf gradient
+ * (straight-through clamp; 0 for an empty pair), written, and
+ * pnr_pairs_to_points_conf adds them per point in pair order -- before ABI 26 the
+ * kernel added them into d_conf[N] with float atomics, whose order, hence the
+ * low bits of the sum, changed from run to run.
  * Any of d_color / d_dir / d_conf may be NULL. */
 int pnr_aggregate_bwd_pairs(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w,
                             const pnr_mlp_bwd* wb, const pnr_agg_saved* saved,
@@ -543,6 +551,12 @@ int pnr_used_points(const int32_t* pidx, const int32_t* n_samples_dev, int32_t K
  * negative point rows (empty pairs) are skipped. */
 int pnr_pairs_to_points(const int32_t* prow_sorted, const int32_t* pair_of, int64_t P, const float* dz1,
                         const int32_t* used_map, float* d_p1, uint32_t* d_p1_absmax, void* stream);
+/* d_conf[p] = sum of dconf_pair[pair] (pnr_aggregate_bwd_pairs' per-pair d_conf)
+ * over the pairs of point p in pair order, from the same grouping (ABI 26):
+ * written for every referenced point, rows of the others untouched (the caller
+ * zeroes d_conf[N]); deterministic. */
+int pnr_pairs_to_points_conf(const int32_t* prow_sorted, const int32_t* pair_of, int64_t P,
+                             const float* dconf_pair, float* d_conf, void* stream);
 /* The block3.0 extras of pnr_aggregate_bwd_pairs_x3 without float atomics (ABI 19;
  * that call skips its own extras pass when pnr_mlp_bwd.w3e is NULL):
  * pnr_aggregate_bwd_extras_rows writes per pair g_pair[pair][0..7] = (g0, g1, g2,
@@ -916,6 +930,49 @@ int pnr_probe(const pnr_rays* rays, const pnr_query_params* q, const pnr_query_b
               const pnr_points* pts, const float* opacity, float* max_opacity, float* max_loc_w,
               float* far_dist, float* avg_color, float* avg_dir, float* avg_conf, float* avg_emb,
               void* stream);
+
+/* ---------------------------------------------------------------- ray batches
+ * Camera rays and training batches made on the device (ABI 26), replacing the
+ * host-side item of the reference's dataset (data/nerf_synth360_ft_dataset.py:546-635,
+ * get_dtu_raydir data/data_utils.py:55-69).
+ *
+ * cams [F,16] fp32, per frame: camrotc2w row-major (9), campos (3), fx, fy, cx, cy.
+ * Directions: x = ((px + 0.5f) - cx) / fx and y likewise, three correctly rounded
+ * fp32 operations each; d_i = (x R[i][0] + y R[i][1]) + R[i][2] in fp64 on the
+ * widened fp32 values, left to right, no FMA, rounded to fp32 once; with dir_norm
+ * the fp64 vector is divided by (|d| + 1e-5) before that rounding.
+ *
+ * Both calls validate on the host before any HIP call, never read device memory
+ * on the host, launch on `stream`, allocate nothing. */
+enum { PNR_RAYS_RANDOM = 0, PNR_RAYS_PATCH = 1, PNR_RAYS_FULL = 2 };
+enum { PNR_BG_CALLER = 0, PNR_BG_WHITE = 1, PNR_BG_BLACK = 2, PNR_BG_RANDOM = 3 };
+
+/* raydir[R,3] of camera row `frame` for R pixels: pixels[R,2] fp32 (x, y), or
+ * NULL = the whole H x W frame in row-major order, x fastest (then R = H * W).
+ * pixel_idx[R,2] (optional) receives the (x, y) used. */
+int pnr_camera_rays(const float* cams, int32_t F, int32_t frame, int32_t H, int32_t W, const float* pixels,
+                    int64_t R, int32_t dir_norm, float* raydir, float* pixel_idx, void* stream);
+
+/* One training batch of the resident stack images[F,H,W,3] (uint8 when
+ * images_u8, else fp32): R = S * S rays (PNR_RAYS_FULL: H * W, S ignored).
+ * state: device int64[2] = {seed, step}; the call reads it on the device and
+ * advances step by one in a one-thread launch queued behind the batch kernel, so
+ * the next call -- or the next replay of a captured graph -- draws the next batch.
+ * Frame: `frame` >= 0, else frame_dev[0] (device int32, clamped to [0, F)), else
+ * (frame < 0 and frame_dev NULL) drawn.
+ * Random numbers: Philox4x32-10, key = (seed lo, seed hi), counter = (i, step lo,
+ * step hi, stream); an integer in [0, n) is the high word of word * n.
+ *   stream 0, i = ray (PNR_RAYS_RANDOM): px = [r0 W], py = [r1 H], with replacement;
+ *   stream 1, i = 0, once per batch: PNR_RAYS_PATCH origin ([r0 (W-S+1)], [r1 (H-S+1)]),
+ *     ray i at (origin x + i % S, origin y + i / S); PNR_BG_RANDOM is white iff
+ *     r2 >= 2^31; the drawn frame is [r3 F].
+ * Outputs: raydir[R,3], pixel_idx[R,2] fp32 (x, y), gt[R,3] fp32 (uint8 / 255.0f,
+ * fp32 copied), campos[3], camrot[3,3], frame_id[1], bg[3] (untouched, and may be
+ * NULL, with PNR_BG_CALLER). */
+int pnr_ray_batch(const void* images, int32_t images_u8, const float* cams, int32_t F, int32_t H, int32_t W,
+                  int64_t* state, int32_t frame, const int32_t* frame_dev, int32_t mode, int32_t S,
+                  int32_t dir_norm, int32_t bg_mode, float* raydir, float* pixel_idx, float* gt, float* campos,
+                  float* camrot, float* bg, int32_t* frame_id, void* stream);
 
 /* -------------------------------------------------------- 2-D neural renderer
  * NeuralRenderer(input_dim=128) (models/neural_render/neural_renderer.py:24-104,

@@ -853,7 +853,7 @@ struct BwdArgs {
   float* d_p1;           // [N,256] (+=)
   float* d_color;        // [N,3] (+=) or null
   float* d_dir;          // [N,3] (+=) or null
-  float* d_conf;         // [N]   (+=) or null
+  float* d_conf;         // [n*8] per pair (written; summed per point by pnr_pairs_to_points_conf) or null
   const void* wx[3];     // k_pairs_bwd<1>: frag_pack_x3 of W4^T, W3[:, :256]^T, W2^T;
                          // k_pairs_bwd<2>: the three pnr_pack_bwd_h2 packs
   const float* wxs;      // k_pairs_bwd<2>: device [3], the packs' scales 2^(s - 11)
@@ -1261,13 +1261,17 @@ __global__ void __launch_bounds__(64 * kPairWaves, 2) k_pairs_bwd(BwdArgs A) {
     if constexpr (V == 2) wave_tile_absmax(acc, tmx + wid);
     __syncthreads();
     // d wt_k = d alpha_s a_k + <d f_s, h4_k>  ->  d conf_k (straight-through clamp, :724-726)
+    // One term per pair, written: the per-point sums follow in pair order
+    // (pnr_pairs_to_points_conf), so d conf does not depend on the order the waves arrive in.
     if (wid == 0 && active && A.d_conf) {
       const int32_t pr = A.sv.prow[pair];
+      float dc = 0.f;
       if (pr >= 0) {
         const float dwt = dalpha * a_k + dotp[lane] + dotp[kTP + lane] + dotp[2 * kTP + lane] +
                           dotp[3 * kTP + lane];
-        atomicAdd(A.d_conf + pr, dwt * A.sv.wn[pair]);
+        dc = dwt * A.sv.wn[pair];
       }
+      A.d_conf[pair] = dc;
     }
     // ---------------------------------------------------------- block3.2^T: dh3 = W4^T dz4
 #pragma unroll
@@ -2557,6 +2561,49 @@ extern "C" int pnr_pairs_to_points(const int32_t* prow_sorted, const int32_t* pa
   if (P == 0) return PNR_OK;
   hipLaunchKernelGGL(k_pairs_to_points, dim3(grid_for(cdiv(P, 64), 4, 2048)), dim3(256), 0, as_stream(stream), prow_sorted,
                      pair_of, P, dz1, used_map, d_p1, d_p1_absmax);
+  PNR_LAUNCH_CHECK();
+  return PNR_OK;
+}
+
+namespace pnr {
+// d conf per point from k_pairs_bwd's per-pair terms: the thread at the first
+// sorted position of a point's run adds the run's terms in pair order (eight
+// loads in flight), so the sum has one order -- bitwise repeatable.
+__global__ void __launch_bounds__(256) k_conf_from_runs(const int32_t* __restrict__ prow_sorted,
+                                                        const int32_t* __restrict__ pair_of, int64_t P,
+                                                        const float* __restrict__ dconf_pair,
+                                                        float* __restrict__ d_conf) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < P; i += stride) {
+    const int32_t pr = prow_sorted[i];
+    if (pr < 0 || (i > 0 && prow_sorted[i - 1] == pr)) continue;
+    float s = 0.f;
+    int64_t j = i;
+    bool more = true;
+    while (more) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const bool in = j + u < P && prow_sorted[j + u] == pr;   // a run is contiguous: once false, false
+        v[u] = in ? dconf_pair[pair_of[j + u]] : 0.f;
+        if (!in) more = false;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += v[u];   // + 0.f past the run's end changes nothing
+      j += 8;
+    }
+    d_conf[pr] = s;
+  }
+}
+}  // namespace pnr
+
+extern "C" int pnr_pairs_to_points_conf(const int32_t* prow_sorted, const int32_t* pair_of, int64_t P,
+                                        const float* dconf_pair, float* d_conf, void* stream) {
+  PNR_CHECK_ARG(P >= 0 && (P == 0 || (prow_sorted && pair_of && dconf_pair && d_conf)),
+                "pairs_to_points_conf: bad args");
+  if (P == 0) return PNR_OK;
+  hipLaunchKernelGGL(k_conf_from_runs, dim3(grid_for(P, 256, 4096)), dim3(256), 0, as_stream(stream), prow_sorted,
+                     pair_of, P, dconf_pair, d_conf);
   PNR_LAUNCH_CHECK();
   return PNR_OK;
 }

@@ -320,7 +320,7 @@ __global__ void __launch_bounds__(256) k_pad_rows32(const float* __restrict__ sr
 
 // ---------------------------------------------------------------- the step's scratch
 struct StepPlan {
-  size_t words, dzc3, dzc2, dzc1, d_hid, vpe32, dz[4], dpa, d_p1, g_pair, prow_sorted, pair_of, grp, x1, dx1, packs,
+  size_t words, dzc3, dzc2, dzc1, d_hid, vpe32, dz[4], dpa, dconf_pair, d_p1, g_pair, prow_sorted, pair_of, grp, x1, dx1, packs,
       pscale, w3e, gemm, absp, acp, bsplit[4], total;
   size_t gemm_bytes, grp_bytes;
 };
@@ -342,6 +342,7 @@ static StepPlan plan_step(int64_t n, int64_t n_used) {
   p.vpe32 = take((size_t)nn * 32 * 4);
   for (int i = 0; i < 4; ++i) p.dz[i] = take((size_t)mm * 256 * 4);
   p.dpa = take((size_t)mm * 4);
+  p.dconf_pair = take((size_t)mm * 4);
   p.d_p1 = take((size_t)nu * 256 * 4);
   p.g_pair = take((size_t)mm * 8 * 4);
   p.prow_sorted = take((size_t)mm * 4);
@@ -506,14 +507,16 @@ extern "C" int pnr_aggregate_bwd_step_h2(const pnr_points* pts, const pnr_sample
   pnr_mlp_bwd_h2 wbh = {packs, packs + per, packs + 2 * per, pscale};
   float* dz[4] = {F(P.dz[0]), F(P.dz[1]), F(P.dz[2]), F(P.dz[3])};
   float* dpa = F(P.dpa);
+  float* dconf_pair = out->d_conf ? F(P.dconf_pair) : nullptr;   // per pair; summed per point below
   PNR_TRY(pnr_aggregate_bwd_pairs_h2(pts, s, w, &wb, &wbh, saved, d_feat, d_hid, dz[0], dz[1], dz[2], dz[3], dpa,
-                                     nullptr, nullptr, nullptr, out->d_conf, sv));
+                                     nullptr, nullptr, nullptr, dconf_pair, sv));
   // ---- per-point sums of dz1 and of the block3.0 extras (pairs grouped by point, pair order)
   int32_t* prow_sorted = reinterpret_cast<int32_t*>(b + P.prow_sorted);
   int32_t* pair_of = reinterpret_cast<int32_t*>(b + P.pair_of);
   const int32_t* off = nullptr;
   PNR_TRY(group_pairs(saved->prow, m, pts->used_map, nk, prow_sorted, pair_of, b + P.grp, P.grp_bytes, st, &off,
                       true));
+  if (dconf_pair) PNR_TRY(pnr_pairs_to_points_conf(prow_sorted, pair_of, m, dconf_pair, out->d_conf, sv));
   float* g_pair = F(P.g_pair);
   PNR_TRY(pnr_aggregate_bwd_extras_rows(pts, s, w, saved, w3e, dz[2], g_pair, sv));
   float* d_p1 = F(P.d_p1);

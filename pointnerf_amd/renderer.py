@@ -408,6 +408,15 @@ class NeuralPointsRayMarching(nn.Module):
                                        False, self._state, ray_cam=ray_cam)
         return out
 
+    def render_camera(self, campos, camrotc2w, intrinsic, H, W, near, far, bg_color, dir_norm=False, **kw):
+        """Render one camera's H x W frame: ``rays.camera_rays`` (pnr_camera_rays:
+        the directions made on the device, no table uploaded) followed by
+        ``render_rays`` with its keyword arguments.  intrinsic: [3,3] or a focal
+        length with the principal point at the frame's centre."""
+        from .rays import camera_rays
+        raydir = camera_rays(intrinsic, camrotc2w, H, W, dir_norm=dir_norm, device=self.neural_points.xyz.device)
+        return self.render_rays(campos, camrotc2w, raydir, near, far, bg_color, **kw)
+
     def render_views(self, views, near, far, bg_color, force_grid=False, events=None, reuse_p1=False, sync=True):
         """Render several frames' ray batches -- views = [(campos [3], camrot
         [3,3], raydir [R_i,3]), ...], e.g. the N band shares one rank renders

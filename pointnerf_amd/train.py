@@ -328,6 +328,9 @@ class AggregateFn(torch.autograd.Function):
         d_color = torch.zeros((N, 3), **f32) if has_c else None
         d_dir = torch.zeros((N, 3), **f32) if has_d else None
         d_conf = torch.zeros(N, **f32) if has_f else None
+        # the pairs' d conf terms, written per pair and summed per point in pair order by
+        # pnr_pairs_to_points_conf below (no float atomics: bitwise repeatable)
+        dconf_pair = torch.empty(Pn, **f32) if has_f else None
         # fp32h2: the dX chain on split-f16 MFMA too (pnr_aggregate_bwd_pairs_h2)
         bwd_h2 = spec.h2 and BWD_H2
         wb, wbx, _keepb = packed_bwd(agg, x3=spec.x3 and not bwd_h2, h2=bwd_h2)
@@ -340,7 +343,7 @@ class AggregateFn(torch.autograd.Function):
         # d_p1 = NULL: the per-point sums of dz1 come from pnr_pairs_to_points below
         # (pairs sorted by point: no atomics, deterministic) instead of the kernel's atomics
         bufs = (L.ptr(d_feat), L.ptr(d_hid), L.ptr(dz1), L.ptr(dz2), L.ptr(dz3), L.ptr(dz4), L.ptr(dpa),
-                None, L.ptr(d_color), L.ptr(d_dir), L.ptr(d_conf), L.stream_ptr(dev))
+                None, L.ptr(d_color), L.ptr(d_dir), L.ptr(dconf_pair), L.stream_ptr(dev))
         if bwd_h2:
             L.check(L.lib().pnr_aggregate_bwd_pairs_h2(ctypes.byref(ctx.pts), ctypes.byref(spec.samples),
                                                        ctypes.byref(ctx.mlp), ctypes.byref(wb), ctypes.byref(wbx),
@@ -359,6 +362,9 @@ class AggregateFn(torch.autograd.Function):
         used_map = None if spec.used is None else spec.used[1]
         # the pairs grouped by point in pair order (torch.sort(prow, stable=True) natively)
         prow_sorted, pair_of = L.group_pairs(sv["prow"][:m], used_map, n_p1 if used_map is not None else N)
+        if has_f:
+            L.check(L.lib().pnr_pairs_to_points_conf(L.ptr(prow_sorted), L.ptr(pair_of), m, L.ptr(dconf_pair),
+                                                     L.ptr(d_conf), L.stream_ptr(dev)), "pnr_pairs_to_points_conf")
         if point_extras:
             g_pair = torch.empty((max(m, 1), 8), **f32)
             L.check(L.lib().pnr_aggregate_bwd_extras_rows(ctypes.byref(ctx.pts), ctypes.byref(spec.samples),
