@@ -398,7 +398,9 @@ int pnr_aggregate_fwd_x3(const pnr_points* pts, const pnr_samples* s, const pnr_
  * Colour branch (point_aggregators.py:630-638): with wc1a..wc3h set it runs on
  * the same f16-split MFMA (k_color_h2; color_branch.0 split into columns
  * 0..143 and 144..279 + bias, both packed with ONE layer scale cscale[0]);
- * with wc1a NULL on the fp32 MFMA (k_color) like pnr_aggregate_fwd. */
+ * with wc1a NULL on the fp32 MFMA (k_color) like pnr_aggregate_fwd.  For this
+ * inference call wc1a set with any of wc1b / wc2h / wc3h NULL is an error
+ * (PNR_EINVAL); the training calls take such a partial set as "no colour packs". */
 typedef struct {
   const void* w1bh;   /* block1.0 columns 224..283                              */
   const void* w2h;    /* block1.2, NO bias column (the kernel adds w->b2 in fp32) */
@@ -492,7 +494,9 @@ int pnr_aggregate_fwd_train_x3(const pnr_points* pts, const pnr_samples* s, cons
  * f16-split MFMA too, k_color_h2 with k_color<train>'s saves (vpe, hc1..hc3),
  * else on the fp32 training kernel), the range flag as pnr_aggregate_fwd_h2: set when an
  * activation left the f16 range, the caller then re-runs the step on
- * pnr_aggregate_fwd_train_x3).  Saved layout and outputs as the fp32 call. */
+ * pnr_aggregate_fwd_train_x3).  Saved layout and outputs as the fp32 call.
+ * Unlike pnr_aggregate_fwd_h2, a partial set of colour packs (any of wc1a..wc3h
+ * NULL) is no error here: the colour branch then runs on the fp32 training kernel. */
 int pnr_aggregate_fwd_train_h2(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w,
                                const pnr_mlp_h2* wh, const pnr_agg_saved* saved, float* out_feat,
                                float* out_weight, float* out_conf, void* scratch, size_t scratch_bytes,

@@ -66,7 +66,7 @@ def _init_seq(seq: nn.Sequential):
         _xavier_(mods[-1], 1.0)
 
 
-PREFETCH_PAD = 8   # kPackPad in aggregate.hip: zero k-steps appended for the weight prefetch
+PREFETCH_PAD = 8   # kPackPad in agg_quad.h: zero k-steps appended for the weight prefetch
 
 
 def _pack_device(kind: int, W: torch.Tensor, bias: torch.Tensor | None, pad: int) -> torch.Tensor:

@@ -1,5 +1,7 @@
-// Device helpers shared by the fp32 (aggregate.hip) and bf16 (aggregate_bf16.hip)
-// aggregation kernels.
+// Device helpers and host declarations shared by the aggregation sources: the
+// fp32 forward and its host plan (aggregate.hip), the split-MFMA forwards
+// (aggregate_x3.hip), the bf16 forward (aggregate_bf16.hip), the backward
+// (aggregate_bwd.hip) and the per-point bookkeeping (aggregate_points.hip).
 #pragma once
 #include "pnr_common.h"
 
@@ -28,6 +30,14 @@ __device__ __forceinline__ float xor8_sum(float v) {
   v += __shfl_xor(v, 2);
   v += __shfl_xor(v, 4);
   return v;
+}
+
+// max |v| over a wave's lanes into an LDS slot (float bits compared as unsigned:
+// a NaN's bits exceed every finite and infinite value, so it propagates).
+__device__ __forceinline__ void wave_absmax_to(unsigned* slot, unsigned mb) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mb = max(mb, (unsigned)__shfl_xor((int)mb, o));
+  if ((threadIdx.x & 63) == 0 && mb) atomicMax(slot, mb);
 }
 
 __device__ __forceinline__ void mat3(const float* R, const float v[3], float o[3]) {
@@ -173,6 +183,10 @@ __device__ __forceinline__ uint4 f16x8_scale2048(const uint4& a) {
   typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   return __builtin_bit_cast(uint4, __builtin_bit_cast(h8, a) * (h8)((_Float16)2048.f));
 }
+
+// aggregate.hip: the saved-activation struct of a training forward, as the
+// backward's entry points check it too.
+int check_saved(const pnr_agg_saved* sv);
 
 // gemm.hip, for the native backward step (train_step.hip): C[:, :ncols] (rows of
 // ldc floats) = A^T B on mode 0 fp32 / 1 fp32x3 / 2 fp32h2 (pnr_gemm_tn*), and

@@ -144,6 +144,7 @@ def test_grid_handle_finaliser_defers_destroy():
     import ctypes
     import gc
     from pointnerf_amd import querier as Q
+    gc.collect()                       # earlier tests' unreachable handles are deferred now, not inside the count below
     h = Q.GridHandle.__new__(Q.GridHandle)
     h.h = ctypes.c_void_p(0x1234)      # never dereferenced: the test takes it back below
     h.self_ref = h                     # a reference cycle: freed by the collector, not by refcount
