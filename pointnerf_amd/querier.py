@@ -177,8 +177,18 @@ class QueryBuffers:
     def fits(self, R, SR, K):
         return self.R == R and self.SR == SR and self.K == K
 
+    def count_ptr(self, slot: int) -> int:
+        """Device address of one of the 8 counters (COUNT_*), for the kernels that read it there."""
+        return self.counts.data_ptr() + 4 * slot
+
+    def samples(self, raydir, n_max: int, ray_cam=None) -> L.Samples:
+        """pnr_samples of this query with room for n_max rows; raydir [R,3] as queried, ray_cam its camera index."""
+        return L.Samples(self.valid_list.data_ptr(), self.count_ptr(COUNT_S_VALID), n_max, self.pidx.data_ptr(),
+                         self.sample_w.data_ptr(), self.sample_p.data_ptr(), raydir.data_ptr(),
+                         self.fill_rs.data_ptr(), self.SR, self.K, L.ptr(ray_cam))
+
     def read_counts(self):
-        """{S_filled, S_valid, R_hit, R_valid, n_pairs, n_cand} (one D2H copy, syncs)."""
+        """{S_filled, S_valid, R_hit, R_valid, n_pairs, n_cand, n_used} (one D2H copy, syncs)."""
         return counts_dict(self.counts.cpu())
 
     def read_counts_async(self) -> "CountsHandle":
@@ -188,11 +198,18 @@ class QueryBuffers:
         return CountsHandle(self.counts)
 
 
-def counts_dict(c: torch.Tensor) -> dict:
-    n_cand = int(c[6:8].view(torch.int64).item())
-    c = c.tolist()
-    return dict(S_filled=c[0], S_valid=c[1], R_hit=c[2], R_valid=c[3], n_pairs=c[4], n_cand=n_cand,
-                n_used=c[5])   # n_used: pnr_used_points' count when the caller put it in counts[5]
+# slots of the 8 int32 counters (pnr_query_bufs.counts) that kernels are pointed at
+COUNT_S_VALID = 1   # valid samples: pnr_samples.n_dev
+COUNT_R_VALID = 3   # rays with a valid sample
+COUNT_N_USED = 5    # pnr_used_points' count (pnr_points.n_used_dev), when the caller put it there
+
+
+def counts_dict(c, n_used: bool = True) -> dict:
+    """The 8 counters (int32 tensor or list) by name, n_cand the int64 in slots 6 and 7; n_used False: without it."""
+    c = c.tolist() if torch.is_tensor(c) else c
+    d = dict(S_filled=c[0], S_valid=c[1], R_hit=c[2], R_valid=c[3], n_pairs=c[4],
+             n_cand=(c[6] & 0xffffffff) | (c[7] << 32))
+    return dict(d, n_used=c[COUNT_N_USED]) if n_used else d
 
 
 class CountsHandle:
@@ -217,7 +234,7 @@ class CountsHandle:
 # hipFree / hipHostFree / hipEventDestroy are illegal there (they invalidate a
 # global-mode capture: GPUTEST_r04's RenderGraph failure).  So __del__ never
 # calls HIP; the handles are destroyed at the next safe point
-# (release_deferred: a handle creation or build, finish(), RenderGraph after
+# (release_deferred: a handle creation or build, a full finish(), RenderGraph after
 # its capture).
 _DEFERRED: list = []
 _CAPTURES = [0]   # RenderGraph captures in progress (any stream of this process)

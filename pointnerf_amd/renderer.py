@@ -17,14 +17,13 @@ the feature buffer) and no ``raypos[R,400,3]`` / ``[R,SR,K,38]`` intermediates.
 """
 from __future__ import annotations
 
-import gc
-
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from .aggregator import PointAggregator
-from .querier import QueryBuffers, lighting_fast_querier
+from .querier import COUNT_R_VALID, camera_tables, counts_dict, lighting_fast_querier, release_deferred
+from .render_eval import EAGER, QUEUED, RayBatch, RenderGraph, _RenderCall, _RenderState, bg_channels  # noqa: F401
 
 
 class NeuralPoints(nn.Module):
@@ -147,47 +146,6 @@ class NeuralPoints(nn.Module):
                 ray_mask, vsize, 0)
 
 
-class _RenderState:
-    """Device buffers one render stream reuses: the query buffers and the
-    aggregate scratch (whose head holds P1, see pnr_points.p1_ready)."""
-
-    def __init__(self):
-        self.bufs = None
-        self.scratch = None
-        self.scratch_key = None
-        self.side = None   # fp32h2: the side stream P1 runs on
-        self.feat = None   # decoded features [rows, 129], reused by every call on this stream
-        self.feat_h = None   # bf16 precision: the same as bf16 rows [rows, L.FEAT_H_PITCH] (uint16)
-
-    def feat_rows(self, rows: int, dev) -> torch.Tensor:
-        """[rows, 129] view of the persistent feature buffer.  The calls of one
-        stream use it in stream order (a call's composite reads it before the
-        next call's aggregate writes it), so it is allocated once and grown by
-        1.5x: a multi-GB allocation inside a frame stalls the launch queue
-        (c5: 20 GB per frame)."""
-        rows = max(int(rows), 1)
-        if self.feat is None or self.feat.shape[0] < rows or self.feat.device != dev:
-            old = 0 if self.feat is None else self.feat.shape[0]
-            self.feat = None
-            self.feat = torch.empty((max(rows, int(1.5 * old)), 129), dtype=torch.float32, device=dev)
-        return self.feat[:rows]
-
-    def feat_h_rows(self, rows: int, dev) -> torch.Tensor:
-        """feat_rows for pnr_aggregate_fwd_bf16_hf's bf16 feature rows."""
-        rows = max(int(rows), 1)
-        if self.feat_h is None or self.feat_h.shape[0] < rows or self.feat_h.device != dev:
-            old = 0 if self.feat_h is None else self.feat_h.shape[0]
-            self.feat_h = None
-            self.feat_h = torch.empty((max(rows, int(1.5 * old)), L.FEAT_H_PITCH), dtype=torch.int16, device=dev)
-        return self.feat_h[:rows]
-
-
-def _counts_dict(c):
-    """The 8 query counters (pnr_query_bufs.counts) as QueryBuffers.read_counts() returns them."""
-    n_cand = (int(c[6]) & 0xffffffff) | (int(c[7]) << 32)
-    return dict(S_filled=c[0], S_valid=c[1], R_hit=c[2], R_valid=c[3], n_pairs=c[4], n_cand=n_cand)
-
-
 # The default is fp32h2, the measured headline path (fp32-accurate: the same
 # render tolerance as fp32, tests/test_gpu_x3.py; an activation beyond f16's range
 # re-renders the call on fp32x3).
@@ -220,7 +178,7 @@ class _ZeroOneConfLoss(torch.autograd.Function):
                                          L.ptr(counts), L.stream_ptr(dev)), "pnr_point_counts")
         part = torch.empty(1024, dtype=torch.float32, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
-        L.check(L.lib().pnr_zero_one_loss_fwd(L.ptr(c), L.ptr(counts), N, L.c_void_p(bufs.counts.data_ptr() + 12),
+        L.check(L.lib().pnr_zero_one_loss_fwd(L.ptr(c), L.ptr(counts), N, L.c_void_p(bufs.count_ptr(COUNT_R_VALID)),
                                               SR * K, eps, L.ptr(part), L.ptr(out), L.stream_ptr(dev)),
                 "pnr_zero_one_loss_fwd")
         ctx.save_for_backward(c, counts, out)
@@ -283,13 +241,12 @@ class NeuralPointsRayMarching(nn.Module):
         if precision not in PRECISIONS:
             raise L.PnrError(f"precision {precision!r}: one of {PRECISIONS}")
         self.precision = precision
-        # render_rays_train's per-pair forward: "fp32x3" (split-bf16 MFMA,
-        # fp32-accurate, the default) or "fp32" (native fp32 MFMA)
-        # training path: fp32h2 (forward chain and the weight / point-half gradient GEMMs on f16-split
-        # MFMA, the measured default) / fp32x3 (split-bf16 MFMA) / fp32
+        # render_rays_train: "fp32h2" (forward chain and the weight / point-half gradient GEMMs on
+        # f16-split MFMA, fp32-accurate: the measured default), "fp32x3" (split-bf16 MFMA,
+        # fp32-accurate) or "fp32" (native fp32 MFMA)
         self.train_precision = "fp32h2"
-        self.p1_side_stream = True        # fp32h2 sync-free calls: P1 beside the query (see _render_rays)
-        self.p1_used_only = True          # bf16: P1 for the referenced points only (see _render_rays)
+        self.p1_side_stream = True        # fp32h2 sync-free calls: P1 beside the query (render_eval: start_p1_side)
+        self.p1_used_only = True          # bf16: P1 for the referenced points only (render_eval: aggregate_chunk)
         # bf16: the aggregated features themselves in bf16 (pnr_aggregate_fwd_bf16_hf ->
         # pnr_composite_fwd_hf: half the feature bytes written and read)
         self.bf16_features = True
@@ -307,7 +264,8 @@ class NeuralPointsRayMarching(nn.Module):
         self.aggregator = aggregator if aggregator is not None else PointAggregator(opt).to(neural_points.device)
         self.chunk_rays = chunk_rays
         self._state = _RenderState()     # query buffers + aggregate scratch of the eager path
-        self._pending = []               # render_rays(sync=False) calls awaiting finish()
+        self._pending = []               # render_rays(sync=False) calls (_PendingCall) awaiting finish()
+        self._done = []                  # counts of calls a synchronous render completed, for the next finish()
         self._sv_per_ray = None          # largest valid samples per ray seen (feature-buffer sizing)
         self.overflow_rerenders = 0
         # fork's 2-D CNN after the composite (neural_points_volumetric_model.py:258-260, 343-344)
@@ -317,6 +275,8 @@ class NeuralPointsRayMarching(nn.Module):
             self.neural_render_2d = NeuralRenderer(input_dim=128).to(neural_points.device)
         self._last_counts = None
         self._train_conf_src = None   # query buffers of the last render_rays_train (zero_one_conf_loss)
+        self.last_train_aux = None    # _TrainAux of the last render_rays_train
+        self._budget_dev = None       # a quarter of the device's memory, once asked for (_train_budget)
         self._rw2c_key = None
         if getattr(opt, "which_render_func", "radiance") != "radiance" or \
                 getattr(opt, "which_blend_func", "alpha") != "alpha" or \
@@ -371,7 +331,9 @@ class NeuralPointsRayMarching(nn.Module):
         ``force_grid``), for the whole launch stream.  The call's own copies of
         its inputs (contiguous rays, camera tables) are made on the query
         stream; the caller makes ``raydir`` / ``campos`` / ``camrot`` /
-        ``ray_cam`` themselves ready on that stream.
+        ``ray_cam`` themselves ready on that stream.  A write to the points
+        that changes neither their storage nor their version (through ``.data``,
+        by a raw-pointer kernel) is not seen: pass ``force_grid=True`` after it.
 
         fp32h2: the f16 split holds activations below 65504 only.  Each call
         reads the launches' range flag once (a 4-byte read after the last
@@ -383,30 +345,27 @@ class NeuralPointsRayMarching(nn.Module):
             # a synchronous call reads (and may clear) the shared range flag and the
             # counts: complete the pending sync-free calls first so none of their
             # checks is lost; their counts stay queued for the caller's next finish()
-            done = self.finish()
-            self._done = done + getattr(self, "_done", [])
+            self._done = self.finish() + self._done
+        batch = RayBatch(campos, camrot, raydir, near, far, bg_color, ray_cam)
         prec = self._precision_now()
+        opts = dict(force_grid=force_grid, events=events)
         if not sync and self._sv_per_ray is not None:
-            out, rec = self._render_rays(prec, campos, camrot, raydir, near, far, bg_color, force_grid, events,
-                                         reuse_p1, self._state, capacity=self._capacity_per_ray(), ray_cam=ray_cam,
-                                         query_stream=query_stream)
-            rec["args"] = (campos, camrot, raydir, near, far, bg_color, force_grid, reuse_p1, ray_cam)
-            rec["out"] = out
-            # what a re-render in finish() must find unchanged (weights, grid)
-            rec["h2_key"] = self.aggregator.h2_key()
-            rec["grid_key"] = self.neural_points.querier.grid.key
+            out, rec = self._render_rays(QUEUED, prec, batch, self._state, reuse_p1=reuse_p1, query_stream=query_stream,
+                                         capacity=self._sv_per_ray * 1.25, **opts)
             self._pending.append(rec)
             return out
         n_ev = len(events) if events is not None else 0
-        out, _ = self._render_rays(prec, campos, camrot, raydir, near, far, bg_color, force_grid, events, reuse_p1,
-                                   self._state, ray_cam=ray_cam)
+        out, _ = self._render_rays(EAGER, prec, batch, self._state, reuse_p1=reuse_p1, **opts)
         if prec == "fp32h2" and not self.aggregator.h2_range_ok():
             self._block_h2()
             if events is not None:
                 del events[n_ev:]
-            out, _ = self._render_rays("fp32x3", campos, camrot, raydir, near, far, bg_color, force_grid, events,
-                                       False, self._state, ray_cam=ray_cam)
+            out, _ = self._render_rays(EAGER, "fp32x3", batch, self._state, **opts)
         return out
+
+    def _render_rays(self, mode, precision, batch, state, **options):
+        """One render call (render_eval._RenderCall and its modes) -> (outputs, its _PendingCall or None)."""
+        return _RenderCall(self, mode, precision, batch, state, **options).run()
 
     def render_camera(self, campos, camrotc2w, intrinsic, H, W, near, far, bg_color, dir_norm=False, **kw):
         """Render one camera's H x W frame: ``rays.camera_rays`` (pnr_camera_rays:
@@ -450,9 +409,6 @@ class NeuralPointsRayMarching(nn.Module):
         self._h2_blocked_key = self.aggregator.h2_key()
         self.h2_fallbacks += 1
 
-    def _capacity_per_ray(self):
-        return self._sv_per_ray * 1.25
-
     def _observe(self, counts, rays):
         r = counts["S_valid"] / max(rays, 1)
         self._sv_per_ray = r if self._sv_per_ray is None else max(self._sv_per_ray, r)
@@ -470,21 +426,20 @@ class NeuralPointsRayMarching(nn.Module):
         the later ones' counts are kept for the next finish()).  Returns the
         per-call sample counts (the ``last_counts`` dict of each call, in issue
         order)."""
-        from .querier import release_deferred
-        release_deferred()
-        done = getattr(self, "_done", [])
+        if upto is None:   # freeing a collected GridHandle synchronises the device: not while later calls stay queued
+            release_deferred()
+        done = self._done
         n_all = len(done) + len(self._pending)
         k = n_all if upto is None else min(int(upto), n_all)
         need = k - len(done)
         if need > 0:
             head = self._pending[:need]
-            head[-1]["event"].synchronize()
+            head[-1].event.synchronize()
             # the range flags as copied to pinned memory behind each call's event (a
             # .item() here would queue behind -- and wait for -- the later calls)
-            if need < len(self._pending) and any(int(r["range_host"][0]) != 0 for r in head
-                                                 if r.get("range_flag") is not None):
+            if need < len(self._pending) and any(int(r.range_host[0]) != 0 for r in head if r.range_flag is not None):
                 head = self._pending
-                head[-1]["event"].synchronize()
+                head[-1].event.synchronize()
             self._pending = self._pending[len(head):]
             done = done + self._complete(head)
         self._done = done[k:]
@@ -492,340 +447,42 @@ class NeuralPointsRayMarching(nn.Module):
 
     def _complete(self, pend):
         """finish()'s checks on calls whose last kernels have completed."""
-        if not pend:
-            return []
-        # every fp32h2 call's own range flag (the packs -- and their flag -- are
-        # rebuilt when the weights change between calls)
-        flags = {}
-        for r in pend:
-            f = r.get("range_flag")
-            if f is not None:
-                bad = int(r["range_host"][0]) != 0   # this call's own copy (taken after its launches)
-                prev = flags.get(f.data_ptr())
-                flags[f.data_ptr()] = (f, bad or (prev is not None and prev[1]))
-        range_bad = any(bad for _, bad in flags.values())
-        if range_bad:
+        # every fp32h2 call's own range flag (the packs, and their flag, are rebuilt when the weights change between
+        # calls), read from the call's pinned copy taken after its launches: the raised ones, by storage
+        h2 = [r for r in pend if r.range_flag is not None]
+        raised = {r.range_flag.data_ptr(): r.range_flag for r in h2 if int(r.range_host[0]) != 0}
+        if raised:
             cur = self.aggregator.h2_key()
-            for f, bad in flags.values():
-                if bad:
-                    f.zero_()
+            for f in raised.values():
+                f.zero_()
             self.aggregator.h2_reset_range()
-            if any(r["h2_key"] == cur for r in pend if r.get("range_flag") is not None):
+            if any(r.h2_key == cur for r in h2):
                 self._h2_blocked_key = cur
             self.h2_fallbacks += 1
         counts = []
         for rec in pend:
             tot = dict(S_filled=0, S_valid=0, R_hit=0, R_valid=0, n_pairs=0, n_cand=0)
             over = False
-            for (cap, rays), h in zip(rec["caps"], rec["host"].tolist()):
-                c = _counts_dict(h)
+            for (cap, rays), h in zip(rec.caps, rec.counts.tolist()):
+                c = counts_dict(h, n_used=False)
                 self._observe(c, rays)
                 over |= c["S_valid"] > cap
                 for k in tot:
                     tot[k] += c[k]
-            f = rec.get("range_flag")
-            rec_bad = f is not None and flags[f.data_ptr()][1]
+            rec_bad = rec.range_flag is not None and rec.range_flag.data_ptr() in raised
             if over or rec_bad:
-                if rec["h2_key"] != self.aggregator.h2_key() or rec["grid_key"] != self.neural_points.querier.grid.key:
+                if rec.h2_key != self.aggregator.h2_key() or rec.grid_key != self.neural_points.querier.grid.key:
                     raise L.PnrError("a render_rays(sync=False) call must be re-rendered, but the weights or the "
                                      "points changed before finish(): call finish() before modifying the model")
-                cp, cr, rd, near, far, bg, fg, reuse, rcam = rec["args"]
-                prec = "fp32x3" if rec_bad else rec["precision"]
-                out, _ = self._render_rays(prec, cp, cr, rd, near, far, bg, fg, None, False, self._state,
-                                           ray_cam=rcam)
-                for dst, src in zip(rec["out"], out):
+                out, _ = self._render_rays(EAGER, "fp32x3" if rec_bad else rec.precision, rec.batch, self._state,
+                                           force_grid=rec.force_grid)
+                for dst, src in zip(rec.out, out):
                     dst.copy_(src)
                 tot = dict(self.last_counts)
                 self.overflow_rerenders += int(over)
             counts.append(tot)
         self.last_counts = counts[-1]
         return counts
-
-    def _render_rays(self, precision, campos, camrot, raydir, near, far, bg_color, force_grid, events, reuse_p1,
-                     state, capacity=None, keep=None, record=True, ray_cam=None, query_stream=None):
-        """One render call.  capacity None: size the feature buffer from this
-        batch's counts (one host sync per chunk); else capacity = valid samples
-        per ray the feature buffer is sized for (no sync; the per-chunk counts
-        are copied to pinned host memory behind an event, returned in the
-        record for finish() / RenderGraph.check())."""
-        opt = self.opt
-        dev = raydir.device
-        L.require_gpu(raydir)
-        np_ = self.neural_points
-        q = np_.querier
-        if force_grid:
-            q.grid.key = None
-        R = raydir.shape[0]
-        SR, K = opt.SR, opt.K
-        C = self.aggregator.C          # 128 (fork) or 3 (upstream RGB head)
-        f32 = dict(dtype=torch.float32, device=dev)
-        ray_color = torch.empty((R, C), **f32)
-        opacity = torch.empty((R, SR), **f32)
-        is_bg = torch.empty((R,), **f32)
-        ray_mask = torch.empty((R,), dtype=torch.int8, device=dev)
-        bg = bg_color.to(dev).float().reshape(-1).contiguous() if bg_color is not None else None
-        if bg is not None and bg.numel() != C:
-            bg = bg.expand(C).contiguous() if bg.numel() == 1 else None
-            if bg is None:
-                raise L.PnrError(f"bg_color must have 1 or {C} channels")
-        from .querier import camera_tables
-        use_qs = query_stream is not None and capacity is not None
-        launch = torch.cuda.current_stream(dev)
-        if use_qs:
-            # The query's inputs are made on query_stream itself (the caller makes
-            # campos / camrot / raydir / ray_cam ready on the launch stream, but the
-            # copies below are this call's own).  The points can change on the launch
-            # stream (an optimizer step on xyz, a forced rebuild): the query stream
-            # then waits for the launch stream before the grid build reads them.
-            xkey = (np_.xyz.data_ptr(), np_.xyz._version)
-            if force_grid or getattr(state, "q_xkey", None) != xkey:
-                query_stream.wait_stream(launch)
-            state.q_xkey = xkey
-            with torch.cuda.stream(query_stream):
-                campos, camrot = camera_tables(campos, camrot, ray_cam)
-                if ray_cam is not None:
-                    ray_cam = ray_cam.to(device=dev, dtype=torch.int32).contiguous()
-                ev_cam = torch.cuda.Event()
-                ev_cam.record(query_stream)
-            # np_.tables and the aggregate read the camera tables on the launch stream
-            # (the query stream's tail is the previous query, which the launch stream
-            # already waited for: no overlap is lost)
-            launch.wait_event(ev_cam)
-            for t in (campos, camrot, ray_cam):
-                if t is not None:
-                    t.record_stream(launch)
-        else:
-            campos, camrot = camera_tables(campos, camrot, ray_cam)
-            if ray_cam is not None:
-                ray_cam = ray_cam.to(device=dev, dtype=torch.int32).contiguous()
-        bf16 = precision == "bf16"
-        mlp, _keepw = self.aggregator.packed_bf16() if bf16 else self.aggregator.packed()
-        mlpx = mlph = _keepx = _keeph = None
-        if precision == "fp32x3":
-            mlpx, _keepx = self.aggregator.packed_x3()
-        elif precision == "fp32h2":
-            mlph, _keeph = self.aggregator.packed_h2()
-        if keep is not None:   # RenderGraph: the captured launches point into these packs
-            keep += [mlp, _keepw, mlpx, _keepx, mlph, _keeph]
-        pts, _keepp = np_.tables(campos, camrot, bf16=bf16)
-        totals = dict(S_filled=0, S_valid=0, R_hit=0, R_valid=0, n_pairs=0, n_cand=0)
-        chunk = max(1, self.chunk_rays or R)
-        n_chunks = max(1, -(-R // chunk))
-        rec = None
-        if capacity is not None:
-            host = torch.empty((n_chunks, 8), dtype=torch.int32, pin_memory=True) if record else None
-            dcounts = None if record else torch.empty((n_chunks, 8), dtype=torch.int32, device=dev)
-            rec = dict(precision=precision, caps=[], host=host, dcounts=dcounts,
-                       range_flag=_keeph["range_flag"] if _keeph is not None else None)
-
-        def mark(stream=None):
-            if events is None:
-                return None
-            e = torch.cuda.Event(enable_timing=True)
-            e.record(stream)
-            return e
-
-        # fp32h2: block1.0's per-point half (P1) depends on the points and weights
-        # only, so it runs on a side stream beside the query (which is latency
-        # bound and leaves the MFMA pipes idle) instead of in front of k_pairs_h2;
-        # the aggregate waits on its event.  Sync-free calls only (their feature
-        # buffer, hence the scratch holding P1, is sized before the query), not
-        # under graph capture.
-        p1_side = None
-        # (only while P1 is the smaller job: P1 costs ~0.5 us per point, the query
-        # ~3.5 us per ray -- measured 0.99 vs 2.25 ms at 2 M points / 640 k rays; at
-        # 10 M points / 1.25 M rays the 5.8 ms P1 outlasted the query and the overlap
-        # gained nothing)
-        if (precision == "fp32h2" and capacity is not None and keep is None and self.p1_side_stream
-                and pts.n <= self.p1_side_max_points_per_ray * R):
-            c0 = min(chunk, R)
-            Sv0 = min(int(c0 * capacity) + 1024, c0 * SR)
-            scr0, ready0 = self._agg_scratch(state, max(Sv0, 1), pts.n, dev, bf16, reuse_p1, precision)
-            if not ready0:
-                if getattr(state, "side", None) is None:
-                    state.side = torch.cuda.Stream(device=dev)
-                main = torch.cuda.current_stream(dev)
-                ev_in = torch.cuda.Event()
-                ev_in.record(main)
-                side = state.side
-                side.wait_event(ev_in)
-                s0 = mark(side)
-                L.check(L.lib().pnr_point_pre_h2(L.ctypes.byref(pts), L.ctypes.byref(mlph), L.ptr(scr0),
-                                                 scr0.numel() * 4, L.c_void_p(side.cuda_stream)), "pnr_point_pre_h2")
-                s1 = mark(side)
-                ev_p1 = torch.cuda.Event()
-                ev_p1.record(side)
-                scr0.record_stream(side)
-                p1_side = ev_p1
-                if events is not None:
-                    events.append(("p1", s0, s1))
-
-        for ci, r0 in enumerate(range(0, R, chunk)):
-            r1 = min(R, r0 + chunk)
-            if use_qs:   # a non-contiguous raydir's copy belongs to the query stream too
-                with torch.cuda.stream(query_stream):
-                    rd = raydir[r0:r1].contiguous()
-                rd.record_stream(launch)
-            else:
-                rd = raydir[r0:r1].contiguous()
-            rc = None if ray_cam is None else ray_cam[r0:r1]
-            slot = None
-            if use_qs:
-                # the query on its own stream, two buffer sets in turn; each set is
-                # reused after the launch-stream work that read it (its event)
-                if getattr(state, "qring", None) is None:
-                    state.qring, state.qfree, state.qslot = [None, None], [None, None], 1
-                slot = state.qslot = state.qslot ^ 1
-                if state.qfree[slot] is not None:
-                    query_stream.wait_event(state.qfree[slot])
-                with torch.cuda.stream(query_stream):
-                    e0 = mark()
-                    bufs, hp, rays, qp = q.run(np_.xyz.detach(), rd, campos, camrot, near, far,
-                                               bufs=state.qring[slot], ray_cam=rc)
-                    e1 = mark()
-                    ev_q = torch.cuda.Event()
-                    ev_q.record(query_stream)
-                state.qring[slot] = bufs
-                torch.cuda.current_stream(dev).wait_event(ev_q)
-            else:
-                e0 = mark()
-                bufs, hp, rays, qp = q.run(np_.xyz.detach(), rd, campos, camrot, near, far, bufs=state.bufs,
-                                           ray_cam=rc)
-                e1 = mark()
-                state.bufs = bufs
-            if capacity is None:
-                cnt = bufs.read_counts()
-                for k in totals:
-                    totals[k] += cnt[k]
-                self._observe(cnt, r1 - r0)
-                Sv = cnt["S_valid"]
-            else:
-                Sv = min(int((r1 - r0) * capacity) + 1024, (r1 - r0) * SR)
-                rec["caps"].append((Sv, r1 - r0))
-            hf = bf16 and C == 128 and self.bf16_features
-            feat = state.feat_h_rows(Sv, dev) if hf else state.feat_rows(Sv, dev)
-            s = L.Samples(bufs.valid_list.data_ptr(), bufs.counts.data_ptr() + 4, Sv, bufs.pidx.data_ptr(),
-                          bufs.sample_w.data_ptr(), bufs.sample_p.data_ptr(), rd.data_ptr(),
-                          bufs.fill_rs.data_ptr(), SR, K, L.ptr(rc))
-            e2 = mark()
-            # bf16 (config c5: 20 M points, a frame references a fraction of them): block1.0's
-            # point half only for the points this batch's neighbour lists reference
-            # (pnr_used_points, device list and count), written at their own rows of the P1
-            # table (pnr_points.used without used_map) -- no indirection in the pairs kernel
-            scratch, ready = self._agg_scratch(state, max(Sv, 1), pts.n, dev, bf16, reuse_p1 or r0 > 0, precision)
-            # (a reuse_p1 call after a used-only one finds the table partial (key
-            # cleared): it computes its own used rows, not the whole table)
-            used_only = (bf16 and self.p1_used_only and n_chunks == 1 and keep is None and not ready)
-            if used_only:
-                pts.used = L.ptr(self._used_points(state, bufs, K, pts.n))
-                pts.n_used, pts.used_map = pts.n, None
-                pts.n_used_dev = bufs.counts.data_ptr() + 5 * 4
-                ready, state.scratch_key = False, None   # the table holds this batch's rows only
-            if p1_side is not None:   # P1 written into this same scratch by the side stream
-                torch.cuda.current_stream(dev).wait_event(p1_side)
-                ready = True
-            pts.p1_ready = int(ready)
-            if bf16:
-                fn = L.lib().pnr_aggregate_fwd_bf16_hf if hf else L.lib().pnr_aggregate_fwd_bf16
-                L.check(fn(L.ctypes.byref(pts), L.ctypes.byref(s), L.ctypes.byref(mlp), L.ptr(feat), None, None,
-                           L.ptr(scratch), scratch.numel() * 4, L.stream_ptr(dev)),
-                        "pnr_aggregate_fwd_bf16")
-            elif precision == "fp32x3":
-                L.check(L.lib().pnr_aggregate_fwd_x3(L.ctypes.byref(pts), L.ctypes.byref(s), L.ctypes.byref(mlp),
-                                                     L.ctypes.byref(mlpx), L.ptr(feat), None, None, L.ptr(scratch),
-                                                     scratch.numel() * 4, L.stream_ptr(dev)),
-                        "pnr_aggregate_fwd_x3")
-            elif precision == "fp32h2":
-                L.check(L.lib().pnr_aggregate_fwd_h2(L.ctypes.byref(pts), L.ctypes.byref(s), L.ctypes.byref(mlp),
-                                                     L.ctypes.byref(mlph), L.ptr(feat), None, None, L.ptr(scratch),
-                                                     scratch.numel() * 4, L.stream_ptr(dev)),
-                        "pnr_aggregate_fwd_h2")
-            else:
-                L.check(L.lib().pnr_aggregate_fwd(L.ctypes.byref(pts), L.ctypes.byref(s), L.ctypes.byref(mlp),
-                                                  L.ptr(feat), None, None, L.ptr(scratch), scratch.numel() * 4,
-                                                  L.stream_ptr(dev)),
-                        "pnr_aggregate_fwd")
-            if C == 3:   # upstream colour head: [alpha, rgb] rows
-                feat = self.aggregator.apply_rgb_head(feat, n_dev=bufs.counts[1:2], n=Sv)
-            e3 = mark()
-            cp = L.CompositeParams(float(opt.vsize[2]), int(opt.raydist_mode_unit), C, L.ptr(bg), max(Sv, 1))
-            comp = L.lib().pnr_composite_fwd_hf if hf else L.lib().pnr_composite_fwd
-            L.check(comp(L.ctypes.byref(rays), L.ctypes.byref(qp), L.ctypes.byref(bufs.c), L.ctypes.byref(cp),
-                         L.ptr(feat), L.ptr(ray_color[r0:r1]), L.ptr(opacity[r0:r1]), L.ptr(is_bg[r0:r1]),
-                         L.ptr(ray_mask[r0:r1]), L.stream_ptr(dev)),
-                    "pnr_composite_fwd")
-            if rec is not None:
-                if record:
-                    rec["host"][ci].copy_(bufs.counts, non_blocking=True)
-                else:
-                    rec["dcounts"][ci].copy_(bufs.counts)
-            if slot is not None:   # the launch stream's last reader of this query-buffer set
-                ev_free = torch.cuda.Event()
-                ev_free.record(torch.cuda.current_stream(dev))
-                state.qfree[slot] = ev_free
-            if events is not None:
-                e4 = mark()
-                events += [("query", e0, e1), ("aggregate", e2, e3), ("composite", e3, e4)]
-        if rec is not None:
-            if record:
-                if rec["range_flag"] is not None:
-                    # the fp32h2 range flag as it stands after this call's launches, to
-                    # pinned memory behind the call's event: finish() reads it without
-                    # a stream sync (which would wait for the calls queued after it)
-                    rec["range_host"] = torch.empty(1, dtype=torch.int32, pin_memory=True)
-                    rec["range_host"].copy_(rec["range_flag"], non_blocking=True)
-                rec["event"] = torch.cuda.Event()
-                rec["event"].record()
-        else:
-            self.last_counts = totals
-        return (ray_color, opacity, is_bg, ray_mask), rec
-
-    @staticmethod
-    def _used_points(state, bufs, K, n_points):
-        """pnr_used_points of a query (count into bufs.counts[5]) on buffers kept in
-        the render state: the device list of referenced point rows."""
-        dev = bufs.pidx.device
-        if getattr(state, "used_n", None) != n_points:
-            i32 = dict(dtype=torch.int32, device=dev)
-            nb = L.c_size_t(0)
-            L.check(L.lib().pnr_used_points_scratch_bytes(n_points, L.ctypes.byref(nb)),
-                    "pnr_used_points_scratch_bytes")
-            state.used_bufs = tuple(torch.empty(n_points, **i32) for _ in range(3)) + (
-                torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=dev),)
-            state.used_n = n_points
-        flags, used_map, used, scr = state.used_bufs
-        cap = bufs.pidx.numel() // K
-        L.check(L.lib().pnr_used_points(L.ptr(bufs.pidx), L.ptr(bufs.counts), K, cap, n_points, L.ptr(flags),
-                                        L.ptr(used_map), L.ptr(used), L.c_void_p(bufs.counts.data_ptr() + 20),
-                                        L.ptr(scr), scr.numel(), L.stream_ptr(dev)), "pnr_used_points")
-        return used
-
-    def _agg_scratch(self, state, n_max, n_points, dev, bf16, reuse, precision="fp32"):
-        """Persistent aggregate scratch (P1 lives at its start, see
-        pnr_points.p1_ready) -> (tensor, P1 already valid).  The P1 is valid
-        when reuse is requested and the embedding storage, block1.0 and the
-        precision match the call that wrote it."""
-        emb = self.neural_points.points_embeding
-        b1 = self.aggregator.block1[0]
-        # fp32h2 computes P1 on f16-split MFMA (k_point_pre_h2), the other fp32 paths on fp32 MFMA
-        key = (bf16, precision == "fp32h2", n_points, emb.data_ptr(), emb._version, b1.weight.data_ptr(),
-               b1.weight._version, b1.bias.data_ptr(), b1.bias._version)
-        need = (L.aggregate_scratch_bf16 if bf16 else L.aggregate_scratch)
-        nb = L.c_size_t(0)
-        fn = L.lib().pnr_aggregate_scratch_bytes_bf16 if bf16 else L.lib().pnr_aggregate_scratch_bytes
-        L.check(fn(int(n_max), int(n_points), L.ctypes.byref(nb)), "aggregate scratch bytes")
-        buf = state.scratch
-        if buf is None or buf.device != dev or buf.numel() * 4 < int(nb.value):
-            # headroom (n_max varies per batch) and geometric growth: no allocation per frame
-            rows = max(int(n_max * 1.5) + 1024, int(1.5 * getattr(state, "scratch_rows", 0)))
-            state.scratch = buf = None
-            buf = need(rows, n_points, dev)
-            state.scratch_rows = rows
-            state.scratch = buf
-            state.scratch_key = None
-        ready = reuse and state.scratch_key == key
-        state.scratch_key = key
-        return buf, ready
 
     @property
     def last_counts(self):
@@ -847,7 +504,7 @@ class NeuralPointsRayMarching(nn.Module):
         pnr_composite_fwd -> pnr_composite_bwd (train.py).  Returns ray_color
         [R,C] (requires grad w.r.t. points_embeding / color / dir / conf and the
         aggregator parameters), opacity [R,SR], is_bg [R], ray_mask [R]."""
-        from .train import AggregateFn, AggSpec, CompositeFn, CompositeSpec, agg_params
+        from .train import AggregateFn, AggSpec, CompositeFn, CompositeSpec, agg_params, used_points_device
         if self.neural_points.points_embeding.dtype != torch.float32:
             raise L.PnrError("training needs an fp32 points_embeding (NeuralPoints(emb_dtype=torch.float32))")
         self._sync_rw2c()
@@ -859,9 +516,7 @@ class NeuralPointsRayMarching(nn.Module):
         R = raydir.shape[0]
         SR, K = opt.SR, opt.K
         C = self.aggregator.C
-        bg = bg_color.to(dev).float().reshape(-1).contiguous() if bg_color is not None else None
-        if bg is not None and bg.numel() == 1:
-            bg = bg.expand(C).contiguous()
+        bg = bg_channels(bg_color, C, dev)
         campos = campos.reshape(3).float().contiguous()
         camrot = camrot.reshape(3, 3).float().contiguous()
         rd = raydir.float().contiguous()
@@ -872,7 +527,6 @@ class NeuralPointsRayMarching(nn.Module):
         # (samples: counts[1], used points: counts[5]) with capacity-sized
         # buffers, and the counts travel to pinned memory behind an event that the
         # backward (or last_counts) waits on -- the forward never drains the GPU.
-        from .train import used_points_device
         used_buf, used_map = used_points_device(bufs, K, xyz.shape[0])
         counts = bufs.read_counts_async()
         self.last_counts = counts
@@ -883,9 +537,7 @@ class NeuralPointsRayMarching(nn.Module):
         if S_cap * TRAIN_BYTES_PER_SAMPLE > self._train_budget(dev):
             S_cap = max(int(bufs.read_counts()["S_valid"]), 1)
             self.train_count_reads += 1
-        s = L.Samples(bufs.valid_list.data_ptr(), bufs.counts.data_ptr() + 4, S_cap, bufs.pidx.data_ptr(),
-                      bufs.sample_w.data_ptr(), bufs.sample_p.data_ptr(), rd.data_ptr(),
-                      bufs.fill_rs.data_ptr(), SR, K)
+        s = bufs.samples(rd, S_cap)
         n = xyz.shape[0]
 
         def tab(t, c):
@@ -942,7 +594,7 @@ class NeuralPointsRayMarching(nn.Module):
         train_memory_budget, or (None) a quarter of the device's memory."""
         if self.train_memory_budget is not None:
             return int(self.train_memory_budget)
-        if getattr(self, "_budget_dev", None) is None:
+        if self._budget_dev is None:
             self._budget_dev = torch.cuda.get_device_properties(dev).total_memory // 4
         return self._budget_dev
 
@@ -994,7 +646,6 @@ class NeuralPointsRayMarching(nn.Module):
         opacity.  conf_coefficient carries no graph here (no_grad render)."""
         np_ = self.neural_points
         dev = raydir.device
-        from .querier import camera_tables
         cp, cr = camera_tables(campos, camrot, None)
         xyz = np_.xyz.detach().contiguous()
         bufs, hp, rays, qp = np_.querier.run(xyz, raydir.float().contiguous(), cp, cr, near, far, bufs=None)
@@ -1014,7 +665,6 @@ class NeuralPointsRayMarching(nn.Module):
         raydir = raydir.reshape(-1, 3).float().contiguous()
         dev = raydir.device
         R, SR = raydir.shape[0], self.opt.SR
-        from .querier import camera_tables
         cp, cr = camera_tables(campos, camrot, None)
         xyz = np_.xyz.detach().contiguous()
         pts, _keep = np_.tables(cp, cr, bf16=True)
@@ -1141,101 +791,3 @@ class NeuralPointsRayMarching(nn.Module):
             out["final_coarse_raycolor"] = self.neural_render_2d(
                 out["coarse_raycolor"].reshape(1, img_h, img_w, -1)).reshape(1, -1, 3)
         return out
-
-
-class RenderGraph:
-    """One ray batch's full render (query -> aggregate -> composite) captured
-    in a HIP graph and replayed without any host work beyond the launch:
-    SURVEY 8(f) rank 2 (the reference syncs at qpiw.py:656, 716 and
-    neural_points.py:786).  The graph owns its query buffers, aggregate
-    scratch and outputs; the camera and ray directions are static input
-    tensors that ``replay`` refreshes in place.  Capture requires an already
-    built grid and fixed weights (the launches point at the current grid
-    tables and weight packs; rebuild the graph after either changes).
-
-    The feature buffer is sized from an eager render of the same batch
-    (valid samples x ``margin``); ``check()`` reads the replay's counts and
-    the fp32h2 range flag (one host sync) and returns False when the replay
-    overflowed that size or an activation left the f16 range -- then render
-    that frame with ``render_rays`` instead."""
-
-    def __init__(self, model: NeuralPointsRayMarching, campos, camrot, raydir, near, far, bg_color,
-                 margin: float = 1.25):
-        L.require_gpu(raydir)
-        self.model = model
-        dev = raydir.device
-        self.campos = campos.reshape(3).float().to(dev).clone()
-        self.camrot = camrot.reshape(3, 3).float().to(dev).clone()
-        self.raydir = raydir.reshape(-1, 3).float().contiguous().clone()
-        self.near, self.far = near, far
-        self.bg = None if bg_color is None else bg_color.to(dev).float().reshape(-1).contiguous().clone()
-        model._sync_rw2c()
-        self.precision = model._precision_now()
-        R = self.raydir.shape[0]
-        chunk = max(1, model.chunk_rays or R)
-        self.state = _RenderState()
-        # eager render: builds nothing new (grid must exist), sizes the buffers
-        model._render_rays(self.precision, self.campos, self.camrot, self.raydir, near, far, self.bg, False, None,
-                           False, self.state)
-        self.eager_counts = dict(model.last_counts)
-        cap = margin * max(self.eager_counts["S_valid"], 1) / max(min(chunk, R), 1)
-        self.keep = []
-        stream = torch.cuda.Stream(dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(stream):   # warm-up on a side stream (allocations, packs)
-            model._render_rays(self.precision, self.campos, self.camrot, self.raydir, near, far, self.bg, False,
-                               None, False, self.state, capacity=cap, record=False)
-        torch.cuda.current_stream(dev).wait_stream(stream)
-        torch.cuda.synchronize(dev)
-        # Nothing may issue a capture-illegal HIP call (hipFree, an event or stream
-        # sync) while the graph records -- from this thread, or from a finaliser
-        # the garbage collector runs at some allocation inside the capture (the
-        # GPUTEST_r04 failure).  Collect dead cycles now, keep the collector off
-        # during the capture, and have GridHandle finalisers defer their frees
-        # (querier._DEFERRED); other threads' calls cannot invalidate a
-        # thread-local capture.
-        from . import querier as Q
-        gc.collect()
-        Q.release_deferred()
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        Q._CAPTURES[0] += 1
-        try:
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.out, self.rec = model._render_rays(self.precision, self.campos, self.camrot, self.raydir, near,
-                                                        far, self.bg, False, None, False, self.state, capacity=cap,
-                                                        keep=self.keep, record=False)
-        finally:
-            Q._CAPTURES[0] -= 1
-            if gc_was_on:
-                gc.enable()
-        Q.release_deferred()
-        self.capacity = cap
-
-    def replay(self, campos=None, camrot=None, raydir=None):
-        """Render the batch again (new camera / rays copied into the static
-        inputs first); returns (ray_color, opacity, is_bg, ray_mask), tensors the
-        graph owns and overwrites on the next replay."""
-        if campos is not None:
-            self.campos.copy_(campos.reshape(3))
-        if camrot is not None:
-            self.camrot.copy_(camrot.reshape(3, 3))
-        if raydir is not None:
-            self.raydir.copy_(raydir.reshape(-1, 3))
-        self.graph.replay()
-        return self.out
-
-    def check(self) -> bool:
-        """True when the last replay's outputs are valid: every chunk's valid
-        samples fit the captured feature buffer and (fp32h2) no activation left
-        the f16 range.  Synchronises."""
-        ok = True
-        for (cap, rays), h in zip(self.rec["caps"], self.rec["dcounts"].cpu().tolist()):
-            c = _counts_dict(h)
-            self.last_counts = c
-            ok &= c["S_valid"] <= cap
-        if self.precision == "fp32h2" and not self.model.aggregator.h2_range_ok():
-            self.model.aggregator.h2_reset_range()
-            ok = False
-        return ok

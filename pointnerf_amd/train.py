@@ -35,6 +35,7 @@ import torch
 
 from . import _lib as L
 from .aggregator import frag_pack, frag_pack_x3
+from .querier import COUNT_N_USED, COUNT_S_VALID
 
 # x3 backward: the block3.0 extras' colour / dir gradients per point inside
 # pnr_pairs_to_points_ex (True, the product).  False hands them to
@@ -141,19 +142,24 @@ def _rows_zeroed(shape, n_dev, device):
     return t
 
 
-def used_points_device(bufs, K: int, n_points: int):
-    """pnr_used_points on a query's buffers, count into bufs.counts[5] (read with
-    the other counts by the caller's one read_counts()): (used [N] buffer,
-    used_map [N]) -- slice used[:n_used] after the read."""
-    dev = bufs.pidx.device
-    i32 = dict(dtype=torch.int32, device=dev)
+def used_points_buffers(n_points: int, device):
+    """(flags, used_map, used, scratch) of pnr_used_points for a table of n_points rows."""
+    i32 = dict(dtype=torch.int32, device=device)
     flags, used_map, used = (torch.empty(n_points, **i32) for _ in range(3))
     nb = L.c_size_t(0)
     L.check(L.lib().pnr_used_points_scratch_bytes(n_points, L.ctypes.byref(nb)), "pnr_used_points_scratch_bytes")
-    scratch = torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=dev)
+    return flags, used_map, used, torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=device)
+
+
+def used_points_device(bufs, K: int, n_points: int, kept=None):
+    """pnr_used_points on a query's buffers, count into bufs.counts[COUNT_N_USED] (read with the other
+    counts by the caller's one read_counts()): (used [N] buffer, used_map [N]) -- slice used[:n_used]
+    after the read.  kept: the caller's used_points_buffers(n_points), reused from call to call."""
+    dev = bufs.pidx.device
+    flags, used_map, used, scratch = kept or used_points_buffers(n_points, dev)
     cap = bufs.pidx.numel() // K
     L.check(L.lib().pnr_used_points(L.ptr(bufs.pidx), L.ptr(bufs.counts), K, cap, n_points, L.ptr(flags),
-                                    L.ptr(used_map), L.ptr(used), L.c_void_p(bufs.counts.data_ptr() + 20),
+                                    L.ptr(used_map), L.ptr(used), L.c_void_p(bufs.count_ptr(COUNT_N_USED)),
                                     L.ptr(scratch), scratch.numel(), L.stream_ptr(dev)), "pnr_used_points")
     return used, used_map
 
@@ -544,7 +550,7 @@ class CompositeFn(torch.autograd.Function):
         spec = ctx.spec
         dev = ctx.feat.device
         if spec.counts is not None and ctx.feat.dim() == 2:   # zero only the device-counted rows
-            d_feat = _rows_zeroed(tuple(ctx.feat.shape), spec.bufs.counts.data_ptr() + 4, dev)
+            d_feat = _rows_zeroed(tuple(ctx.feat.shape), spec.bufs.count_ptr(COUNT_S_VALID), dev)
         else:
             d_feat = torch.zeros_like(ctx.feat)
         if d_color is None:

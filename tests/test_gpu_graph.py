@@ -135,6 +135,68 @@ def test_side_stream_p1_equals_sync(cuda):
             assert _eq(w, g)
 
 
+def _chunked(sc, cuda, precision):
+    """The test renderer with five ray chunks per 1600-ray call, the last one partial."""
+    m = _renderer(sc, cuda, formula_params(salt=0.4))
+    m.chunk_rays = 333
+    m.precision = precision
+    return m
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_chunked_async_equals_chunked_sync(cuda, precision):
+    """A chunked call (chunk_rays below the batch) through sync=False: the chunk
+    loop shared with the synchronous render gives its outputs bitwise and its
+    counts summed over the chunks.  fp32h2: P1 once per call on the side stream,
+    every chunk's aggregate behind it, also when the scratch is used again."""
+    sc, cams = _cams(cuda)
+    m = _chunked(sc, cuda, precision)
+    h2 = precision == "fp32h2"
+    if h2:
+        m.p1_side_max_points_per_ray = 1e9   # the test scene has more points than rays
+    bg = torch.from_numpy(sc["bg"]).to(cuda)
+    want, counts = [], []
+    for cp, cr, rd in cams:
+        want.append([t.clone() for t in m.render_rays(cp, cr, rd, 2.0, 6.0, bg)])
+        counts.append(dict(m.last_counts))
+    for _ in range(2 if h2 else 1):
+        evs = [[] if h2 else None for _ in cams]
+        got = [m.render_rays(cp, cr, rd, 2.0, 6.0, bg, sync=False, events=ev) for (cp, cr, rd), ev in zip(cams, evs)]
+        assert len(m._pending) == 2
+        assert m.finish() == counts
+        assert m.overflow_rerenders == 0
+        for w, g in zip(want, got):
+            assert _eq(w, g)
+        for ev in evs if h2 else ():
+            names = [name for name, _, _ in ev]
+            assert names.count("p1") == 1
+            assert [names.count(k) for k in ("query", "aggregate", "composite")] == [5, 5, 5]
+
+
+@pytest.mark.parametrize("precision", ["fp32h2", "bf16"])
+def test_chunked_query_stream_equals_sync(cuda, precision):
+    """A chunked call with query_stream=: every chunk's query on the second
+    stream, the two buffer sets taken in turn across chunks and calls -- three
+    queued calls over two cameras give the synchronous renders bitwise, and an
+    overflowing call is re-rendered in place."""
+    sc, cams = _cams(cuda)
+    m = _chunked(sc, cuda, precision)
+    bg = torch.from_numpy(sc["bg"]).to(cuda)
+    want = [[t.clone() for t in m.render_rays(cp, cr, rd, 2.0, 6.0, bg)] for cp, cr, rd in cams]
+    qs = torch.cuda.Stream(cuda)
+    torch.cuda.synchronize()
+    order = [0, 1, 0]
+    got = [m.render_rays(*cams[i], 2.0, 6.0, bg, sync=False, query_stream=qs) for i in order]
+    m.finish()
+    for i, g in zip(order, got):
+        assert _eq(want[i], g)
+    m._sv_per_ray = 0.01   # the next call overflows its feature buffer
+    r0 = m.overflow_rerenders
+    g = m.render_rays(*cams[1], 2.0, 6.0, bg, sync=False, query_stream=qs)
+    m.finish()
+    assert m.overflow_rerenders == r0 + 1 and _eq(want[1], g)
+
+
 def test_async_overflow_rerenders_in_place(cuda):
     """A sync-free call whose valid samples outgrow the estimated feature
     buffer is composited memory-safely (rows past the buffer never read) and
@@ -224,6 +286,7 @@ def test_render_graph_capture_survives_finaliser(cuda, precision):
     (an explicit collection at the captured call): the capture stays valid and
     the replay equals the eager render bitwise."""
     from pointnerf_amd import querier as Q
+    from pointnerf_amd.render_eval import CAPTURE
     from pointnerf_amd.renderer import RenderGraph
     sc, cams = _cams(cuda, thetas=(30.0,))
     m = _renderer(sc, cuda, formula_params(salt=0.6))
@@ -235,12 +298,12 @@ def test_render_graph_capture_survives_finaliser(cuda, precision):
     seen = []
     holder = _grid_in_cycle(cuda, sc)
 
-    def render_with_finaliser(*a, **kw):
-        if kw.get("keep") is not None:        # the captured call
+    def render_with_finaliser(mode, *a, **kw):
+        if mode is CAPTURE:                   # the captured call
             holder.clear()                    # the handle becomes cyclic garbage mid-capture
             seen.append(gc.collect())
             seen.append(len(Q._DEFERRED))
-        return orig(*a, **kw)
+        return orig(mode, *a, **kw)
 
     m._render_rays = render_with_finaliser
     g = RenderGraph(m, cp, cr, rd, 2.0, 6.0, bg, margin=1.5)

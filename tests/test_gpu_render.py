@@ -112,3 +112,16 @@ def test_reuse_p1_across_batches(cuda, precision):
     stale_check = m.render_rays(cp2, cr2, rd2[::2].contiguous(), 2.0, 6.0, bg, reuse_p1=True)[0]
     new2 = m.render_rays(cp2, cr2, rd2[::2].contiguous(), 2.0, 6.0, bg)[0]
     assert torch.equal(stale_check, new2) and not torch.equal(new2, new)
+
+
+def test_train_render_refuses_bg_channels(cuda):
+    """render_rays_train refuses a bg_color of neither 1 nor C channels on the
+    host, before the query (no grid is built, no query buffers are kept) -- the
+    composite kernel would read C floats from it."""
+    from pointnerf_amd._lib import PnrError
+    sc = scene(5000, H=8, W=8)
+    m = _renderer(sc, cuda, formula_params()).train()
+    cp, cr, rd = (torch.from_numpy(sc[k]).to(cuda) for k in ("campos", "camrot", "raydir"))
+    with pytest.raises(PnrError, match="bg_color must have 1 or 128 channels"):
+        m.render_rays_train(cp, cr, rd, 2.0, 6.0, torch.zeros(2, device=cuda))
+    assert m.neural_points.querier.grid.key is None and m._train_conf_src is None
