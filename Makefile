@@ -17,8 +17,9 @@ build/%.o: $(SRC_DIR)/%.hip $(SRC_DIR)/pnr_common.h $(SRC_DIR)/agg_common.h $(SR
 
 # The query kernels must round exactly like the reference's fp32 ops: no FMA contraction.
 build/query.o build/grid.o build/voxelize.o: HIPFLAGS += -ffp-contract=off
-# The ray directions are a rounding contract: no FMA contraction either.
-build/rays.o: HIPFLAGS += -ffp-contract=off
+# The ray directions and the seeding votes and samples
+# are rounding contracts: no FMA contraction either.
+build/rays.o build/seed.o: HIPFLAGS += -ffp-contract=off
 # The bf16 pair kernel's gather math (weights, distances, PE) without FMA
 # contraction: its render and general instantiations then round every fp32 op
 # the same way, so their features agree bit for bit (test_gpu_bf16.py).

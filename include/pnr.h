@@ -50,6 +50,11 @@
  *   pnr_camera_rays,
  *   pnr_ray_batch        <- the dataset item: pixel picks, get_dtu_raydir, ground truth, bg coin
  *                           data/nerf_synth360_ft_dataset.py:546-635, data/data_utils.py:55-69
+ *   pnr_alpha_bits,
+ *   pnr_seed_mask,
+ *   pnr_seed_view        <- the geometric part of the point initialisation: ranges box, alpha_masking,
+ *                           nearest_view, the per-view colour / direction lookup
+ *                           run/train_ft.py:42-51, 678-740, models/mvs/mvs_utils.py:573-607
  */
 #ifndef PNR_H_
 #define PNR_H_
@@ -63,7 +68,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 26
+#define PNR_ABI_VERSION 27
 
 enum {
   PNR_OK = 0,
@@ -1097,6 +1102,48 @@ int pnr_vox_closest_scratch_bytes(int64_t n, size_t* out);
 int pnr_vox_closest(const float* xyz_dev, int64_t n, int32_t vox_res, float* centroid, int32_t* grid_idx,
                     int64_t* min_idx, int32_t* inv_idx, int32_t* counts, void* scratch, size_t scratch_bytes,
                     void* stream);
+
+/* ------------------------------------------------------- point seeding (ABI 27)
+ * The geometric part of the reference's initialisation (run/train_ft.py:678-740)
+ * on a raw cloud xyz [N,3] and the posed views of a camera table cams [F,16]
+ * (pnr_camera_rays' rows).  Camera coordinates c = Rc2w^T (p - campos); the
+ * continuous pixel position (u, v) = (fx cx / cz + cx0, fy cy / cz + cy0), pixel
+ * (i, j) covering [i, i+1) x [j, j+1); fp32, one rounding per operation.
+ *
+ * pnr_alpha_bits: alphas [F,H,W] (fp32, or uint8 read as / 255 when alphas_u8)
+ * thresholded at > 0.1 into bit planes: bits[(f H + y) pitch_words + x / 32] bit
+ * x % 32, pitch_words = ceil(W / 32), padding bits 0.  bits_words: uint32 entries
+ * at bits, at least F H pitch_words.
+ *
+ * pnr_seed_mask: keep[n] = 1 when point n lies in the closed box ranges_host
+ * (host float[6] = lo xyz, hi xyz; NULL or ranges_host[0] <= -99: no box) and
+ * passes every view: near_far_host (host float[2] or NULL) asks near - 1 <= cz
+ * <= far; bits (or NULL: no hull vote) asks the bit of pixel (floor u, floor v).
+ * A point outside the image or with cz <= 0 passes the view when inall_img == 0;
+ * with inall_img != 0 the pixel is clamped to the border (cz > 0) or the point is
+ * carved (cz <= 0).  Then the stable compaction: src_idx[0 .. *count) = the
+ * survivors in input order.  keep and src_idx hold out_cap >= N entries; count
+ * is one device int32.  No host sync.
+ *
+ * pnr_seed_view: for each of the M points xyz [M,3]: cam_ind = argmin_f |d| / 200
+ * + (1.1 - d^ . camdir_f), d = p - campos_f, d^ = d / (|d| + 1e-6), camdir_f the
+ * normalised direction of pixel (W / 2, H / 2) (pnr_camera_rays with dir_norm),
+ * lowest index on ties; dirs = d^ of that view; color = the bilinear sample of
+ * images [F,H,W,3] (fp32, or uint8 read as / 255) at (u, v), texel centres at
+ * + 0.5, taps clamped to the border; in_view = 0 and color = 0 when cz <= 0 or
+ * (u, v) lies outside [0, W) x [0, H).  Outputs hold out_cap >= M points; M = 0
+ * launches nothing. */
+#define PNR_SEED_CAM_TILE 64   /* cameras staged in LDS at a time by the two point kernels */
+int pnr_alpha_bits(const void* alphas, int32_t alphas_u8, int32_t F, int32_t H, int32_t W, uint32_t* bits,
+                   int32_t pitch_words, int64_t bits_words, void* stream);
+int pnr_seed_scratch_bytes(int64_t N, size_t* out);
+int pnr_seed_mask(const float* xyz, int64_t N, const float* cams, int32_t F, int32_t H, int32_t W,
+                  const uint32_t* bits, int32_t pitch_words, const float* ranges_host, const float* near_far_host,
+                  int32_t inall_img, int32_t* keep, int32_t* src_idx, int64_t out_cap, int32_t* count,
+                  void* scratch, size_t scratch_bytes, void* stream);
+int pnr_seed_view(const float* xyz, int64_t M, const void* images, int32_t images_u8, const float* cams, int32_t F,
+                  int32_t H, int32_t W, int32_t* cam_ind, float* dirs, float* color, uint8_t* in_view,
+                  int64_t out_cap, void* stream);
 
 /* ------------------------------------------------------------- optimizer */
 /* One Adam step (torch.optim.Adam, amsgrad = False: the optimizer of the

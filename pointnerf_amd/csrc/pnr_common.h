@@ -108,6 +108,40 @@ __device__ __forceinline__ void world_to_pers(const float p[3], const float c[3]
   out[2] = xc[2];
 }
 
+// One row of the device camera table (rays.py camera_table): camrotc2w 9,
+// campos 3, fx, fy, cx, cy.
+constexpr int kCamRow = 16;
+
+struct __attribute__((packed, aligned(4))) Row3 {
+  float x, y, z;
+};
+struct __attribute__((packed, aligned(4))) Row2 {
+  float x, y;
+};
+
+// get_dtu_raydir of one pixel (data/data_utils.py:55-69):
+// x = ((px + 0.5f) - cx) / fx in three correctly rounded fp32 operations, the
+// rotation in fp64 on the widened fp32 entries, (x R[i][0] + y R[i][1]) +
+// R[i][2] left to right without FMA, one rounding to fp32.
+__device__ __forceinline__ Row3 pixel_dir(float px, float py, const float* __restrict__ cam, int dir_norm) {
+  const float x = __fdiv_rn(__fsub_rn(__fadd_rn(px, 0.5f), cam[14]), cam[12]);
+  const float y = __fdiv_rn(__fsub_rn(__fadd_rn(py, 0.5f), cam[15]), cam[13]);
+  double d[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double a = __dmul_rn((double)x, (double)cam[i * 3]);
+    const double b = __dmul_rn((double)y, (double)cam[i * 3 + 1]);
+    d[i] = __dadd_rn(__dadd_rn(a, b), (double)cam[i * 3 + 2]);
+  }
+  if (dir_norm) {   // dirs / (norm + 1e-5), data_utils.py:64-66
+    const double n2 = __dadd_rn(__dadd_rn(__dmul_rn(d[0], d[0]), __dmul_rn(d[1], d[1])), __dmul_rn(d[2], d[2]));
+    const double den = __dadd_rn(__dsqrt_rn(n2), 1e-5);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) d[i] = __ddiv_rn(d[i], den);
+  }
+  return Row3{(float)d[0], (float)d[1], (float)d[2]};
+}
+
 // Seeded reservoir of the grid build (max_o / P overflow, qpiw.py:289-298,
 // 377-384): a uniform random subset chosen by the smallest keys
 // hash32(seed, id) << 32 | id (oracle/query_ref.c states the same keys).

@@ -14,7 +14,6 @@
 namespace pnr {
 
 constexpr int kRBlock = 256;
-constexpr int kCamRow = 16;   // camrotc2w 9, campos 3, fx, fy, cx, cy
 
 // ------------------------------------------------------------------ Philox
 struct U4 {
@@ -45,32 +44,7 @@ __host__ __device__ inline U4 batch_random(int64_t seed, int64_t step, uint32_t 
 }
 
 // -------------------------------------------------------------- directions
-struct __attribute__((packed, aligned(4))) Row3 {
-  float x, y, z;
-};
-struct __attribute__((packed, aligned(4))) Row2 {
-  float x, y;
-};
-
-__device__ __forceinline__ Row3 pixel_dir(float px, float py, const float* __restrict__ cam, int dir_norm) {
-  const float x = __fdiv_rn(__fsub_rn(__fadd_rn(px, 0.5f), cam[14]), cam[12]);
-  const float y = __fdiv_rn(__fsub_rn(__fadd_rn(py, 0.5f), cam[15]), cam[13]);
-  double d[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double a = __dmul_rn((double)x, (double)cam[i * 3]);
-    const double b = __dmul_rn((double)y, (double)cam[i * 3 + 1]);
-    d[i] = __dadd_rn(__dadd_rn(a, b), (double)cam[i * 3 + 2]);
-  }
-  if (dir_norm) {   // dirs / (norm + 1e-5), data_utils.py:64-66
-    const double n2 = __dadd_rn(__dadd_rn(__dmul_rn(d[0], d[0]), __dmul_rn(d[1], d[1])), __dmul_rn(d[2], d[2]));
-    const double den = __dadd_rn(__dsqrt_rn(n2), 1e-5);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) d[i] = __ddiv_rn(d[i], den);
-  }
-  return Row3{(float)d[0], (float)d[1], (float)d[2]};
-}
-
+// (pixel_dir, the arithmetic above, lives in pnr_common.h: seed.hip shares it)
 struct CamRaysArgs {
   const float* cam;      // the frame's row of the camera table
   const float* pixels;   // [R,2] (x, y) or nullptr: the H x W frame, x fastest
