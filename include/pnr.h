@@ -55,6 +55,9 @@
  *   pnr_seed_view        <- the geometric part of the point initialisation: ranges box, alpha_masking,
  *                           nearest_view, the per-view colour / direction lookup
  *                           run/train_ft.py:42-51, 678-740, models/mvs/mvs_utils.py:573-607
+ *   pnr_depth_fuse,
+ *   pnr_depth_points     <- the geometric filter of gen_points: posed depth maps to a cloud
+ *                           models/mvs/filter_utils.py:157-297 (filter_by_masks_gpu)
  */
 #ifndef PNR_H_
 #define PNR_H_
@@ -68,7 +71,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 27
+#define PNR_ABI_VERSION 28
 
 enum {
   PNR_OK = 0,
@@ -1144,6 +1147,65 @@ int pnr_seed_mask(const float* xyz, int64_t N, const float* cams, int32_t F, int
 int pnr_seed_view(const float* xyz, int64_t M, const void* images, int32_t images_u8, const float* cams, int32_t F,
                   int32_t H, int32_t W, int32_t* cam_ind, float* dirs, float* color, uint8_t* in_view,
                   int64_t out_cap, void* stream);
+
+/* --------------------------------------------------- depth-map fusion (ABI 28)
+ * The geometric filter of the reference's gen_points (filter_by_masks_gpu,
+ * models/mvs/filter_utils.py:157-291) on depths [F,H,W] (fp32) and the camera
+ * table cams [F,16], with the conventions of the seeding calls above: c = Rc2w^T
+ * (p - campos), depth = cz, (u, v) = (fx cx / cz + cx0, fy cy / cz + cy0), pixel
+ * (i, j) has its centre at (i + 0.5, j + 0.5).  The point of the continuous pixel
+ * position (x, y) of a view at depth d is
+ *   P(x, y, d) = R (((x - cx0) / fx) d, ((y - cy0) / fy) d, d) + campos
+ * (sub, div, mul; each row ((R0 a + R1 b) + R2 d) + campos).  fp32, one rounding
+ * per operation in the order written, IEEE division and square root.
+ *
+ * A pixel with d <= 0 or non-finite d is invalid: it produces nothing (depth_avg,
+ * count, visible, keep = 0) and tests nothing.  For a valid pixel (r; i, j), p =
+ * P_r(i + 0.5, j + 0.5, d), and each source view s != r in ascending s:
+ *  1. c' = cam_s(p), (u, v) its pixel position; visible when cz' > 0 and (u, v) in
+ *     [0, W) x [0, H); otherwise no match.
+ *  2. d_s = the bilinear sample of depths[s] at (u, v), texel centres at + 0.5,
+ *     taps clamped to the border (pnr_seed_view's sampler); no match when any of
+ *     the four taps is invalid.
+ *  3. c'' = cam_r(P_s(u, v, d_s)), (u'', v'') its pixel position; a match when cz''
+ *     > 0, sqrt((u'' - (i + 0.5))^2 + (v'' - (j + 0.5))^2) < pix_thresh and
+ *     |cz'' - d| / d < rel_thresh.
+ * count = matches, visible = visible views, depth_avg = (d + sum) / (count + 1)
+ * with sum = 0 + cz'' of the matches in ascending s.
+ * keep = valid, count >= geo_cnsst_num (skipped when F == 1), conf > conf_thresh
+ * (conf [F,H,W] fp32 or NULL), mask != 0 (mask [F,H,W] uint8 or NULL), and
+ * P_r(i + 0.5, j + 0.5, depth_avg) inside the closed box ranges (lo xyz, hi xyz;
+ * ranges[0] <= -99: no box).
+ *
+ * pnr_depth_fuse writes depth_avg (fp32), count, visible and keep (int32, all
+ * [F,H,W]), then the stable compaction: src[0 .. *count_dev) = the flat pixels (f
+ * H + j) W + i of the survivors in ascending order.  F H W < 2^31; keep and src
+ * hold cap >= F H W entries; count_dev is one device int32; scratch from
+ * pnr_depth_fuse_scratch_bytes.  No host sync, no allocation.
+ *
+ * pnr_depth_points: for the M survivors of src: xyz = P_r(i + 0.5, j + 0.5,
+ * depth_avg), conf_out = conf (or 1), times 1 - 1 / 1.14869^clamp(count -
+ * geo_cnsst_num + 1, 1, 10) when reassign_conf (filter_utils.py:294-297; the ten
+ * factors in double on the host, rounded to fp32), src_pixel = the flat pixel
+ * (int64), count_out = its count.  Outputs hold out_cap >= M points; M = 0
+ * launches nothing. */
+typedef struct {
+  float pix_thresh;       /* > 0; the reference: 1 */
+  float rel_thresh;       /* > 0; the reference: 0.01 */
+  float conf_thresh;      /* read when conf is given */
+  int32_t geo_cnsst_num;  /* >= 0 */
+  int32_t reassign_conf;
+  float ranges[6];
+} pnr_fuse_params;
+int pnr_depth_fuse_scratch_bytes(int32_t F, int32_t H, int32_t W, size_t* out);
+int pnr_depth_fuse(const float* depths, const float* conf, const uint8_t* mask, const float* cams, int32_t F,
+                   int32_t H, int32_t W, const pnr_fuse_params* params_host, float* depth_avg, int32_t* count,
+                   int32_t* visible, int32_t* keep, int32_t* src, int64_t cap, int32_t* count_dev, void* scratch,
+                   size_t scratch_bytes, void* stream);
+int pnr_depth_points(const int32_t* src, int64_t M, const float* depth_avg, const int32_t* count_map,
+                     const float* conf, const float* cams, int32_t F, int32_t H, int32_t W,
+                     const pnr_fuse_params* params_host, float* xyz, float* conf_out, int64_t* src_pixel,
+                     int32_t* count_out, int64_t out_cap, void* stream);
 
 /* ------------------------------------------------------------- optimizer */
 /* One Adam step (torch.optim.Adam, amsgrad = False: the optimizer of the

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PNR_LIB", os.path.join(_HERE, "libpnr.so"))
 c_int, c_int8, c_int32, c_int64 = ctypes.c_int, ctypes.c_int8, ctypes.c_int32, ctypes.c_int64
 c_float, c_size_t, c_void_p = ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 PNR_OK, PNR_EINVAL, PNR_EOVERFLOW, PNR_EHIP, PNR_ENOMEM = 0, 1, 2, 3, 4
-ABI_VERSION = 27
+ABI_VERSION = 28
 SEED_CAM_TILE = 64   # PNR_SEED_CAM_TILE (include/pnr.h)
 FEAT_H_PITCH = 136   # PNR_FEAT_H_PITCH: uint16 per bf16 feature row (pnr_aggregate_fwd_bf16_hf)
 HEAD_BWD_BLOCKS = 512   # PNR_HEAD_BWD_BLOCKS (include/pnr.h)
@@ -154,6 +154,11 @@ class AggParams(ctypes.Structure):
 class AggGrads(ctypes.Structure):
     _fields_ = [("g", c_void_p * 16), ("d_emb", c_void_p), ("d_color", c_void_p), ("d_dir", c_void_p),
                 ("d_conf", c_void_p)]
+
+
+class FuseParams(ctypes.Structure):
+    _fields_ = [("pix_thresh", c_float), ("rel_thresh", c_float), ("conf_thresh", c_float),
+                ("geo_cnsst_num", c_int32), ("reassign_conf", c_int32), ("ranges", c_float * 6)]
 
 
 class MlpBwdH2(ctypes.Structure):
@@ -327,6 +332,12 @@ SIGNATURES = {
                               c_void_p]),
     "pnr_seed_view": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "pnr_depth_fuse_scratch_bytes": (c_int, [c_int32, c_int32, c_int32, P(c_size_t)]),
+    "pnr_depth_fuse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, P(FuseParams),
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t,
+                               c_void_p]),
+    "pnr_depth_points": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                 P(FuseParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "pnr_scan_scratch_bytes": (c_int, [c_int64, P(c_size_t)]),
     "pnr_exclusive_scan_i32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_size_t, c_void_p]),

@@ -142,6 +142,25 @@ __device__ __forceinline__ Row3 pixel_dir(float px, float py, const float* __res
   return Row3{(float)d[0], (float)d[1], (float)d[2]};
 }
 
+// (u, v) = (fx cx / cz + cx0, fy cy / cz + cy0): the continuous pixel position
+// of a camera-space point; pixel (i, j) covers [i, i+1) x [j, j+1).
+__device__ __forceinline__ void project(const float xc[3], const float* cam, float* u, float* v) {
+  *u = __fadd_rn(__fdiv_rn(__fmul_rn(cam[12], xc[0]), xc[2]), cam[14]);
+  *v = __fadd_rn(__fdiv_rn(__fmul_rn(cam[13], xc[1]), xc[2]), cam[15]);
+}
+
+__device__ __forceinline__ bool in_image(float u, float v, int W, int H) {   // false for NaN
+  return u >= 0.f && u < (float)W && v >= 0.f && v < (float)H;
+}
+
+// Bilinear blend of four taps with weights (wx, wy) towards c01 / c10.
+__device__ __forceinline__ float lerp2(float c00, float c01, float c10, float c11, float wx, float wy) {
+  const float ux = __fsub_rn(1.f, wx), uy = __fsub_rn(1.f, wy);
+  const float top = __fadd_rn(__fmul_rn(ux, c00), __fmul_rn(wx, c01));
+  const float bot = __fadd_rn(__fmul_rn(ux, c10), __fmul_rn(wx, c11));
+  return __fadd_rn(__fmul_rn(uy, top), __fmul_rn(wy, bot));
+}
+
 // Seeded reservoir of the grid build (max_o / P overflow, qpiw.py:289-298,
 // 377-384): a uniform random subset chosen by the smallest keys
 // hash32(seed, id) << 32 | id (oracle/query_ref.c states the same keys).

@@ -65,17 +65,6 @@ struct SeedMaskArgs {
   int32_t* keep;          // [N] 1 = survivor
 };
 
-// (u, v) = (fx cx / cz + cx0, fy cy / cz + cy0): the continuous pixel position
-// of a camera-space point; pixel (i, j) covers [i, i+1) x [j, j+1).
-__device__ __forceinline__ void project(const float xc[3], const float* cam, float* u, float* v) {
-  *u = __fadd_rn(__fdiv_rn(__fmul_rn(cam[12], xc[0]), xc[2]), cam[14]);
-  *v = __fadd_rn(__fdiv_rn(__fmul_rn(cam[13], xc[1]), xc[2]), cam[15]);
-}
-
-__device__ __forceinline__ bool in_image(float u, float v, int W, int H) {   // false for NaN
-  return u >= 0.f && u < (float)W && v >= 0.f && v < (float)H;
-}
-
 __global__ void __launch_bounds__(kSeedBlock) k_seed_mask(SeedMaskArgs a) {
   __shared__ float cam_s[kSeedTile * kCamRow];
   const int64_t n = (int64_t)blockIdx.x * kSeedBlock + threadIdx.x;
@@ -157,13 +146,6 @@ __device__ __forceinline__ Row3 texel(const SeedViewArgs& a, int f, int y, int x
     return Row3{__fdiv_rn((float)q[0], 255.0f), __fdiv_rn((float)q[1], 255.0f), __fdiv_rn((float)q[2], 255.0f)};
   }
   return *reinterpret_cast<const Row3*>(static_cast<const float*>(a.images) + at);
-}
-
-__device__ __forceinline__ float lerp2(float c00, float c01, float c10, float c11, float wx, float wy) {
-  const float ux = __fsub_rn(1.f, wx), uy = __fsub_rn(1.f, wy);
-  const float top = __fadd_rn(__fmul_rn(ux, c00), __fmul_rn(wx, c01));
-  const float bot = __fadd_rn(__fmul_rn(ux, c10), __fmul_rn(wx, c11));
-  return __fadd_rn(__fmul_rn(uy, top), __fmul_rn(wy, bot));
 }
 
 __global__ void __launch_bounds__(kSeedBlock) k_seed_view(SeedViewArgs a) {
