@@ -382,13 +382,22 @@ def ptr(t: torch.Tensor | None):
     return None if t is None else c_void_p(t.data_ptr())
 
 
+def scratch(name: str, *args, device, floats: bool = False) -> torch.Tensor:
+    """The device scratch a ``<name>`` size query (pnr_*_scratch_bytes, or with
+    floats pnr_*_scratch_floats) asks for with args: a uint8 tensor of that many
+    bytes, rounded up to 16 (never empty; any element type can view it) -- its
+    numel() is the byte count to hand to the call -- or that many floats."""
+    n = (c_int64 if floats else c_size_t)(0)
+    check(getattr(lib(), name)(*args, ctypes.byref(n)), name)
+    if floats:
+        return torch.empty(int(n.value), dtype=torch.float32, device=device)
+    return torch.empty(max(-(-int(n.value) // 16) * 16, 16), dtype=torch.uint8, device=device)
+
+
 def aggregate_scratch(n_max: int, n_points: int, device) -> torch.Tensor:
     """Device scratch for pnr_aggregate_fwd(_masked): per-point block1 partial
-    products, K-summed features, masks."""
-    nb = c_size_t(0)
-    check(lib().pnr_aggregate_scratch_bytes(int(n_max), int(n_points), ctypes.byref(nb)),
-          "pnr_aggregate_scratch_bytes")
-    return torch.empty((int(nb.value) + 15) // 16 * 4, dtype=torch.float32, device=device)
+    products, K-summed features, masks (fp32 elements: numel() * 4 bytes)."""
+    return scratch("pnr_aggregate_scratch_bytes", int(n_max), int(n_points), device=device).view(torch.float32)
 
 
 class H2Gemm:
@@ -400,9 +409,7 @@ class H2Gemm:
         # [0]: the range flag; [1:]: pre-zeroed absmax words for fused producers
         self.words = torch.zeros(8, dtype=torch.int32, device=device)
         self.flag = self.words[:1]
-        n = ctypes.c_int64(0)
-        check(lib().pnr_absmax_scratch_floats(ctypes.byref(n)), "pnr_absmax_scratch_floats")
-        self.part = torch.empty(int(n.value), dtype=torch.float32, device=device)
+        self.part = scratch("pnr_absmax_scratch_floats", device=device, floats=True)
 
     def absmax(self, A: torch.Tensor) -> torch.Tensor:
         """[1] int32 holding the float bits of max |A| (device, no sync)."""
@@ -422,20 +429,18 @@ def gemm_tn(A: torch.Tensor, B: torch.Tensor, colsum: bool = False, x3: bool = T
     K, M = A.shape
     N = B.shape[1]
     assert B.shape[0] == K and A.stride(1) == 1 and B.stride(1) == 1
-    nb = c_size_t(0)
-    check(lib().pnr_gemm_tn_scratch_bytes(K, M, N, ctypes.byref(nb)), "pnr_gemm_tn_scratch_bytes")
-    scratch = torch.empty(max(int(nb.value) // 4, 1), dtype=torch.float32, device=A.device)
+    scr = scratch("pnr_gemm_tn_scratch_bytes", K, M, N, device=A.device)
     C = torch.empty((M, N), dtype=torch.float32, device=A.device)
     cs = torch.empty(M, dtype=torch.float32, device=A.device) if colsum else None
     if h2 is not None:
         am = a_absmax if a_absmax is not None else h2.absmax(A)
         check(lib().pnr_gemm_tn_h2(ptr(A), A.stride(0), ptr(B), B.stride(0), K, M, N, ptr(C), ptr(cs), ptr(am),
-                                   ptr(h2.flag), ptr(scratch), scratch.numel() * 4, stream_ptr(A.device)),
+                                   ptr(h2.flag), ptr(scr), scr.numel(), stream_ptr(A.device)),
               "pnr_gemm_tn_h2")
         return (C, cs) if colsum else C
     fn = lib().pnr_gemm_tn_x3 if x3 else lib().pnr_gemm_tn
-    check(fn(ptr(A), A.stride(0), ptr(B), B.stride(0), K, M, N, ptr(C), ptr(cs), ptr(scratch),
-             scratch.numel() * 4, stream_ptr(A.device)), "pnr_gemm_tn")
+    check(fn(ptr(A), A.stride(0), ptr(B), B.stride(0), K, M, N, ptr(C), ptr(cs), ptr(scr), scr.numel(),
+             stream_ptr(A.device)), "pnr_gemm_tn")
     return (C, cs) if colsum else C
 
 
@@ -444,13 +449,10 @@ def group_pairs(prow: torch.Tensor, key_map: torch.Tensor | None, n_keys: int):
     (pnr_group_pairs -- torch.sort(prow, stable=True) with the empty pairs last)."""
     m = prow.numel()
     dev = prow.device
-    nb = c_size_t(0)
-    check(lib().pnr_group_pairs_scratch_bytes(m, max(int(n_keys), 1), ctypes.byref(nb)),
-          "pnr_group_pairs_scratch_bytes")
-    scratch = torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=dev)
+    scr = scratch("pnr_group_pairs_scratch_bytes", m, max(int(n_keys), 1), device=dev)
     ps, po = (torch.empty(max(m, 1), dtype=torch.int32, device=dev) for _ in range(2))
-    check(lib().pnr_group_pairs(ptr(prow), m, ptr(key_map), max(int(n_keys), 1), ptr(ps), ptr(po), ptr(scratch),
-                                scratch.numel(), stream_ptr(dev)), "pnr_group_pairs")
+    check(lib().pnr_group_pairs(ptr(prow), m, ptr(key_map), max(int(n_keys), 1), ptr(ps), ptr(po), ptr(scr),
+                                scr.numel(), stream_ptr(dev)), "pnr_group_pairs")
     return ps[:m], po[:m]
 
 
@@ -480,10 +482,7 @@ def gemm_nn(A: torch.Tensor, B: torch.Tensor, act: torch.Tensor | None = None, s
 
 
 def aggregate_scratch_bf16(n_max: int, n_points: int, device) -> torch.Tensor:
-    nb = c_size_t(0)
-    check(lib().pnr_aggregate_scratch_bytes_bf16(int(n_max), int(n_points), ctypes.byref(nb)),
-          "pnr_aggregate_scratch_bytes_bf16")
-    return torch.empty((int(nb.value) + 15) // 16 * 4, dtype=torch.float32, device=device)
+    return scratch("pnr_aggregate_scratch_bytes_bf16", int(n_max), int(n_points), device=device).view(torch.float32)
 
 
 def stream_ptr(device=None):
@@ -496,9 +495,7 @@ def weighted_colsum(w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     w = w.reshape(-1).float().contiguous()
     x = x.reshape(w.numel(), x.shape[-1]).float().contiguous()
     C = x.shape[1]
-    n = ctypes.c_int64(0)
-    check(lib().pnr_weighted_colsum_scratch_floats(C, ctypes.byref(n)), "pnr_weighted_colsum_scratch_floats")
-    part = torch.empty(int(n.value), dtype=torch.float32, device=x.device)
+    part = scratch("pnr_weighted_colsum_scratch_floats", C, device=x.device, floats=True)
     out = torch.empty(C, dtype=torch.float32, device=x.device)
     check(lib().pnr_weighted_colsum(ptr(w), ptr(x), w.numel(), C, ptr(out), ptr(part), stream_ptr(x.device)),
           "pnr_weighted_colsum")

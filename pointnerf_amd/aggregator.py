@@ -622,8 +622,8 @@ class PointAggregator(nn.Module):
         if torch.is_grad_enabled() and (any(t.requires_grad for t in diff) or
                                         any(p.requires_grad for p in self.parameters())):
             # training path: autograd through pnr_aggregate_fwd_train / _bwd_pairs (train.py)
-            from .train import AggSpec, AggregateFn, agg_params
-            spec = AggSpec(self, s, rows, dict(xyz=keep["xyz"], pers=keep["pers"], rw2c=rw_pairs),
+            from .train import AggSpec, AggregateFn, PointTables, agg_params
+            spec = AggSpec(self, s, rows, PointTables(keep["xyz"], pers=keep["pers"], rw2c=rw_pairs),
                            pair_mask=keep["mask"], keep=(keep, rw_pairs))
             out = AggregateFn.apply(spec, sampled_embedding.reshape(-1, 32).float(),
                                     None if sampled_color is None else sampled_color.reshape(-1, 3).float(),

@@ -75,9 +75,7 @@ def fuse_depth_maps(depths, frames: FrameSet, conf=None, mask=None, geo_cnsst_nu
     prm = fuse_params(geo_cnsst_num, conf_thresh, pix_thresh, rel_thresh, ranges, reassign_conf)
     F, H, W = frames.F, frames.h, frames.w
     n = F * H * W
-    nb = L.c_size_t(0)
-    L.check(L.lib().pnr_depth_fuse_scratch_bytes(F, H, W, ctypes.byref(nb)), "pnr_depth_fuse_scratch_bytes")
-    scratch = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+    scratch = L.scratch("pnr_depth_fuse_scratch_bytes", F, H, W, device=dev)
     depth_avg = torch.empty((F, H, W), dtype=torch.float32, device=dev)
     count_map, visible_map = (torch.empty((F, H, W), dtype=torch.int32, device=dev) for _ in range(2))
     keep, src = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))

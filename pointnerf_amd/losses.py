@@ -55,13 +55,6 @@ def _ld(t2: torch.Tensor) -> int:
     return int(t2.stride(0)) if t2.shape[0] > 1 else int(t2.shape[1])
 
 
-def _scratch(fn, name, dev):
-    nb = L.c_size_t(0)
-    L.check(fn(ctypes.byref(nb)), name)
-    # int64 elements: 8-byte aligned
-    return torch.empty((int(nb.value) + 7) // 8, dtype=torch.int64, device=dev), int(nb.value)
-
-
 class _ColorLosses(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gt, ray_mask, extra_mask):
@@ -86,9 +79,10 @@ class _ColorLosses(torch.autograd.Function):
                 raise L.PnrError(f"color_losses: extra_mask holds {em.numel()} rays, x {R}")
         out = torch.empty(4, dtype=torch.float32, device=dev)
         counts = torch.empty(4, dtype=torch.int64, device=dev)
-        scratch, nb = _scratch(L.lib().pnr_color_loss_scratch_bytes, "pnr_color_loss_scratch_bytes", dev)
+        scratch = L.scratch("pnr_color_loss_scratch_bytes", device=dev)
         L.check(L.lib().pnr_color_loss_fwd(L.ptr(x2), _ld(x2), L.ptr(g2), _ld(g2), L.ptr(rm), L.ptr(em), R, C,
-                                           L.ptr(out), L.ptr(counts), L.ptr(scratch), nb, L.stream_ptr(dev)),
+                                           L.ptr(out), L.ptr(counts), L.ptr(scratch), scratch.numel(),
+                                           L.stream_ptr(dev)),
                 "pnr_color_loss_fwd")
         ctx.save_for_backward(x2, g2, rm, counts)
         ctx.em = em
@@ -138,9 +132,9 @@ class _SparseConfLoss(torch.autograd.Function):
         wfix = torch.empty(N, dtype=torch.int64, device=dev)
         out = torch.empty(1, dtype=torch.float32, device=dev)
         state = torch.empty(1, dtype=torch.float64, device=dev)
-        scratch, nb = _scratch(L.lib().pnr_sparse_loss_scratch_bytes, "pnr_sparse_loss_scratch_bytes", dev)
+        scratch = L.scratch("pnr_sparse_loss_scratch_bytes", device=dev)
         L.check(L.lib().pnr_sparse_loss_fwd(ctypes.byref(qp), ctypes.byref(bufs.c), bufs.R, L.ptr(xyz), L.ptr(c), N,
-                                            L.ptr(wfix), L.ptr(out), L.ptr(state), L.ptr(scratch), nb,
+                                            L.ptr(wfix), L.ptr(out), L.ptr(state), L.ptr(scratch), scratch.numel(),
                                             L.stream_ptr(dev)), "pnr_sparse_loss_fwd")
         if c is not None:
             ctx.save_for_backward(c, wfix, state)

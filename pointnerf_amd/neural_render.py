@@ -152,14 +152,11 @@ class NeuralRenderer(nn.Module):
         out = torch.empty((H * W, 3), dtype=torch.float32, device=x.device)
         h2 = self.precision == "fp32h2"
         sfx = "_h2" if h2 else ""
-        nb = L.c_size_t(0)
-        L.check(getattr(L.lib(), f"pnr_neural_render{sfx}_scratch_bytes")(H, W, L.ctypes.byref(nb)),
-                "pnr_neural_render_scratch_bytes")
-        scratch = torch.empty(max(int(nb.value) // 4, 4), dtype=torch.float32, device=x.device)
+        scratch = L.scratch(f"pnr_neural_render{sfx}_scratch_bytes", H, W, device=x.device)
         w, _keep = self.packed_h2() if h2 else self.packed()
         L.check(getattr(L.lib(), f"pnr_neural_render_fwd{sfx}")(
-            L.ptr(xc), H, W, L.ctypes.byref(w), L.ptr(out), L.ptr(scratch), scratch.numel() * 4,
-            L.stream_ptr(x.device)), "pnr_neural_render_fwd")
+            L.ptr(xc), H, W, L.ctypes.byref(w), L.ptr(out), L.ptr(scratch), scratch.numel(),
+            L.stream_ptr(x.device)), f"pnr_neural_render_fwd{sfx}")
         return out, xc, scratch
 
     def forward(self, x):
@@ -192,16 +189,13 @@ class NeuralRenderFn(torch.autograd.Function):
         d_out = d_out.reshape(H * W, 3).float().contiguous()
         wt, _keep = mod.packed_t_h2() if ctx.h2 else mod.packed_t()
         sfx = "_h2" if ctx.h2 else ""
-        nb = L.c_size_t(0)
-        L.check(getattr(L.lib(), f"pnr_neural_render_bwd{sfx}_scratch_bytes")(H, W, L.ctypes.byref(nb)),
-                "pnr_neural_render_bwd_scratch_bytes")
-        scratch = torch.empty(max(int(nb.value) // 4, 4), **f32)
+        scratch = L.scratch(f"pnr_neural_render_bwd{sfx}_scratch_bytes", H, W, device=dev)
         d_x = torch.empty((H * W, 128), **f32)
         dws = [torch.empty(M * 9 * cin + M, **f32) for M, cin in ((96, 128), (64, 64), (32, 32))]
         L.check(getattr(L.lib(), f"pnr_neural_render_bwd{sfx}")(L.ptr(xc), L.ptr(fscr), L.ptr(out), L.ptr(d_out), H, W,
                                               L.ctypes.byref(wt), L.ptr(d_x), *(L.ptr(d) for d in dws),
-                                              L.ptr(scratch), scratch.numel() * 4, L.stream_ptr(dev)),
-                "pnr_neural_render_bwd")
+                                              L.ptr(scratch), scratch.numel(), L.stream_ptr(dev)),
+                f"pnr_neural_render_bwd{sfx}")
 
         def split(dw, M, cin, cout):
             w = dw[: M * 9 * cin].view(M, 3, 3, cin).permute(0, 3, 1, 2)

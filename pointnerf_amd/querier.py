@@ -165,9 +165,7 @@ class QueryBuffers:
         self.sample_w = torch.empty(max(RS, 1) * 3, dtype=torch.float32, device=device)
         self.sample_p = torch.empty(max(RS, 1) * 3, dtype=torch.float32, device=device)
         self.counts = torch.zeros(8, **i32)
-        nbytes = L.c_size_t(0)
-        L.check(L.lib().pnr_query_scratch_bytes(R, SR, L.ctypes.byref(nbytes)), "pnr_query_scratch_bytes")
-        self.scratch = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=device)
+        self.scratch = L.scratch("pnr_query_scratch_bytes", R, SR, device=device)
         self.c = L.QueryBufs(
             L.ptr(self.n_filled), L.ptr(self.slot_d), L.ptr(self.ray_off), L.ptr(self.fill_rs),
             L.ptr(self.pidx), L.ptr(self.valid_off), L.ptr(self.valid_list), L.ptr(self.vflag),

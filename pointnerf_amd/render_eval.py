@@ -269,15 +269,15 @@ class _RenderCall:
         # fp32h2 computes P1 on f16-split MFMA (k_point_pre_h2), the other fp32 paths on fp32 MFMA
         key = (self.bf16, self.precision == "fp32h2", n_points, emb.data_ptr(), emb._version, b1.weight.data_ptr(),
                b1.weight._version, b1.bias.data_ptr(), b1.bias._version)
+        # the one size query that allocates nothing: the persistent scratch is kept while it is large enough
+        query = "pnr_aggregate_scratch_bytes_bf16" if self.bf16 else "pnr_aggregate_scratch_bytes"
         nb = L.c_size_t(0)
-        fn = L.lib().pnr_aggregate_scratch_bytes_bf16 if self.bf16 else L.lib().pnr_aggregate_scratch_bytes
-        L.check(fn(int(n_max), int(n_points), L.ctypes.byref(nb)), "aggregate scratch bytes")
+        L.check(getattr(L.lib(), query)(int(n_max), int(n_points), L.ctypes.byref(nb)), query)
         if st.scratch is None or st.scratch.device != dev or st.scratch.numel() * 4 < int(nb.value):
             # headroom (n_max varies per batch) and geometric growth: no allocation per frame
             st.scratch_rows = max(int(n_max * 1.5) + 1024, int(1.5 * st.scratch_rows))
             st.scratch = st.scratch_key = None
-            alloc = L.aggregate_scratch_bf16 if self.bf16 else L.aggregate_scratch
-            st.scratch = alloc(st.scratch_rows, n_points, dev)
+            st.scratch = L.scratch(query, st.scratch_rows, int(n_points), device=dev).view(torch.float32)
         ready = reuse and st.scratch_key == key
         st.scratch_key = key
         return st.scratch, ready

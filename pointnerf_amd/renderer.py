@@ -24,6 +24,7 @@ from . import _lib as L
 from .aggregator import PointAggregator
 from .querier import COUNT_R_VALID, camera_tables, counts_dict, lighting_fast_querier, release_deferred
 from .render_eval import EAGER, QUEUED, RayBatch, RenderGraph, _RenderCall, _RenderState, bg_channels  # noqa: F401
+from .render_train import TRAIN_BYTES_PER_SAMPLE, _TrainAux, _TrainCall, march_aux  # noqa: F401
 
 
 class NeuralPoints(nn.Module):
@@ -195,43 +196,6 @@ class _ZeroOneConfLoss(torch.autograd.Function):
         return d, None, None, None, None
 
 
-# device bytes a training batch reserves per sample slot: the forward's kept activations
-# (train.Saved: 8 pairs x (h1..h4, PE_5, extras, masks, weights) + the sample's colour
-# rows) and the backward's dz1..dz4 rows (train.AggregateFn.backward)
-TRAIN_BYTES_PER_SAMPLE = 8 * (4 * 1024 + 256 + 128 + 128 + 16) + 2660 + 8 * (4 * 1024 + 4) + 1024
-
-
-class _TrainAux(dict):
-    """render_rays_train's last_train_aux: keys whose values need the batch's
-    host counts are computed when first read (so that the forward itself never
-    waits for the GPU); ``"k" in aux`` is true for them without computing."""
-
-    def __init__(self):
-        super().__init__()
-        self._lazy = {}
-
-    def lazy(self, keys, fn):
-        for k in keys:
-            self._lazy[k] = fn
-
-    def __contains__(self, k):
-        return dict.__contains__(self, k) or k in self._lazy
-
-    def __missing__(self, k):
-        fn = self._lazy.get(k)
-        if fn is None:
-            raise KeyError(k)
-        vals = fn()
-        for kk in list(self._lazy):
-            if self._lazy[kk] is fn:
-                del self._lazy[kk]
-        self.update(vals)
-        return dict.__getitem__(self, k)
-
-    def get(self, k, default=None):
-        return self[k] if k in self else default
-
-
 class NeuralPointsRayMarching(nn.Module):
     """neural_points_volumetric_model.NeuralPointsRayMarching, fused HIP path."""
 
@@ -276,7 +240,7 @@ class NeuralPointsRayMarching(nn.Module):
         self._last_counts = None
         self._train_conf_src = None   # query buffers of the last render_rays_train (zero_one_conf_loss)
         self.last_train_aux = None    # _TrainAux of the last render_rays_train
-        self._budget_dev = None       # a quarter of the device's memory, once asked for (_train_budget)
+        self._budget_dev = None       # a quarter of the device's memory, once asked for (render_train.train_budget)
         self._rw2c_key = None
         if getattr(opt, "which_render_func", "radiance") != "radiance" or \
                 getattr(opt, "which_blend_func", "alpha") != "alpha" or \
@@ -501,102 +465,11 @@ class NeuralPointsRayMarching(nn.Module):
         """Differentiable render of one training ray batch [R,3] (SURVEY 8(a)
         a17): same query / aggregate / composite as render_rays, with autograd
         through pnr_aggregate_fwd_train -> pnr_aggregate_bwd_pairs and
-        pnr_composite_fwd -> pnr_composite_bwd (train.py).  Returns ray_color
+        pnr_composite_fwd -> pnr_composite_bwd (train.py; the call's stages:
+        render_train._TrainCall).  Returns ray_color
         [R,C] (requires grad w.r.t. points_embeding / color / dir / conf and the
         aggregator parameters), opacity [R,SR], is_bg [R], ray_mask [R]."""
-        from .train import AggregateFn, AggSpec, CompositeFn, CompositeSpec, agg_params, used_points_device
-        if self.neural_points.points_embeding.dtype != torch.float32:
-            raise L.PnrError("training needs an fp32 points_embeding (NeuralPoints(emb_dtype=torch.float32))")
-        self._sync_rw2c()
-        opt = self.opt
-        dev = raydir.device
-        L.require_gpu(raydir)
-        np_ = self.neural_points
-        q = np_.querier
-        R = raydir.shape[0]
-        SR, K = opt.SR, opt.K
-        C = self.aggregator.C
-        bg = bg_channels(bg_color, C, dev)
-        campos = campos.reshape(3).float().contiguous()
-        camrot = camrot.reshape(3, 3).float().contiguous()
-        rd = raydir.float().contiguous()
-        xyz = np_.xyz.detach().contiguous()
-        bufs, hp, rays, qp = q.run(xyz, rd, campos, camrot, near, far, bufs=None)
-        # block1.0's point half only for the points this batch references (device
-        # list and count).  No host read here: the kernels take the device counts
-        # (samples: counts[1], used points: counts[5]) with capacity-sized
-        # buffers, and the counts travel to pinned memory behind an event that the
-        # backward (or last_counts) waits on -- the forward never drains the GPU.
-        used_buf, used_map = used_points_device(bufs, K, xyz.shape[0])
-        counts = bufs.read_counts_async()
-        self.last_counts = counts
-        # saved activations (train.Saved) and the backward's dz rows are sized by the
-        # sample capacity: every slot of the batch (R * SR, no host read) while that
-        # fits the memory budget, else this batch's valid-sample count (one host read)
-        S_cap = R * SR
-        if S_cap * TRAIN_BYTES_PER_SAMPLE > self._train_budget(dev):
-            S_cap = max(int(bufs.read_counts()["S_valid"]), 1)
-            self.train_count_reads += 1
-        s = bufs.samples(rd, S_cap)
-        n = xyz.shape[0]
-
-        def tab(t, c):
-            return None if t is None else t.reshape(n, c)
-
-        used = (used_buf, used_map, bufs.counts[5:6])
-        if self.train_precision not in ("fp32", "fp32x3", "fp32h2"):
-            raise L.PnrError(f"train_precision {self.train_precision!r}: 'fp32h2', 'fp32x3' or 'fp32'")
-        spec = AggSpec(self.aggregator, s, S_cap, dict(xyz=xyz, campos=campos, camrot=camrot, rw2c=np_.rw2c_table()),
-                       keep=(bufs, rd),
-                       used=used, x3=self.train_precision == "fp32x3", h2=self.train_precision == "fp32h2",
-                       counts=counts)
-        spec.keep_saved = self.keep_train_saved
-        feat = AggregateFn.apply(spec, np_.points_embeding.reshape(n, 32), tab(np_.points_color, 3),
-                                 tab(np_.points_dir, 3), tab(np_.points_conf, 1),
-                                 np_.xyz if np_.xyz.requires_grad else None, *agg_params(self.aggregator))
-        if spec.h2_fallback:
-            self.h2_fallbacks += 1
-        if C == 3:
-            feat = self.aggregator.apply_rgb_head(feat, n_dev=bufs.counts[1:2], n=S_cap)
-        cp = L.CompositeParams(float(opt.vsize[2]), int(opt.raydist_mode_unit), C, None)
-        cspec = CompositeSpec(rays, qp, bufs, cp, R, SR, C, keep=(campos, camrot, rd, hp), counts=counts)
-        # bg: differentiable (the fork optimises bg_color, mvs_points_volumetric_model.py:92-94)
-        out = CompositeFn.apply(cspec, feat, bg)
-        self._train_conf_src = bufs
-        aux = _TrainAux()
-        # rows of the point table this batch can give a gradient: the referenced
-        # points, and point 0 (empty slots gather it in conf_coefficient) --
-        # parallel.GradReducer reduces only these across ranks
-        # (unique: pnr_used_points lists each referenced point once, ascending; the
-        # appended point 0 is dropped (-1) when it is already referenced).  Read
-        # when asked for (the used count is a host value).
-
-        def touched():
-            nu = counts.get()["n_used"]
-            u = used_buf[:nu].long()
-            zero = torch.zeros(1, dtype=torch.long, device=dev)
-            if nu:
-                zero = torch.where(u[:1] == 0, zero - 1, zero)
-            return {"touched_rows": torch.cat([u, zero]), "touched_count": nu + 1}
-
-        aux.lazy(("touched_rows", "touched_count"), touched)
-        if self.keep_train_saved:
-            aux["saved"] = spec.saved
-        if np_.points_conf is not None or self.wants_aux():
-            op = out[1]
-            aux.lazy(("weight", "blend_weight", "sample_pidx", "conf_coefficient"),
-                     lambda: self._march_aux(rays, qp, bufs, R, counts.get()["R_valid"], xyz, op))
-        self.last_train_aux = aux
-        return out
-
-    def _train_budget(self, dev) -> int:
-        """Bytes of per-sample training buffers a sync-free forward may reserve:
-        train_memory_budget, or (None) a quarter of the device's memory."""
-        if self.train_memory_budget is not None:
-            return int(self.train_memory_budget)
-        if self._budget_dev is None:
-            self._budget_dev = torch.cuda.get_device_properties(dev).total_memory // 4
-        return self._budget_dev
+        return _TrainCall(self, campos, camrot, raydir, near, far, bg_color).run()
 
     def wants_aux(self) -> bool:
         """The reference aggregator returns weight / conf_coefficient (and the
@@ -606,37 +479,6 @@ class NeuralPointsRayMarching(nn.Module):
         o = self.opt
         return (getattr(o, "sparse_loss_weight", 0) > 0 or "conf_coefficient" in getattr(o, "zero_one_loss_items", ())
                 or getattr(o, "prob", 0) != 0)
-
-    def _march_aux(self, rays, qp, bufs, R, Rv, xyz, opacity):
-        """weight [1,R'',SR,K] (detached: the aggregator's normalised weight),
-        blend_weight [1,R'',SR,1] (detached), conf_coefficient [1,R'',SR,K]
-        (gradiant_clamp of the gathered conf: straight-through gradient to
-        points_conf, point_aggregators.py:724-726, 810-813; empty slots gather
-        point 0 as torch.clamp(pidx, 0) does; 1 without a conf table) and
-        sample_pidx, in pnr_query_compact's row order -- the reference's
-        [1, R'', SR, ...] tensors of the same rays."""
-        opt, np_ = self.opt, self.neural_points
-        SR, K = opt.SR, opt.K
-        dev = opacity.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        pidx = torch.empty((1, Rv, SR, K), dtype=torch.int32, device=dev)
-        scratch3 = [torch.empty((1, Rv, SR, 3), **f32) for _ in range(3)]
-        rmask = torch.empty((1, R), dtype=torch.int8, device=dev)
-        L.check(L.lib().pnr_query_compact(L.ctypes.byref(rays), L.ctypes.byref(qp), L.ctypes.byref(bufs.c), Rv,
-                                          L.ptr(pidx), L.ptr(scratch3[0]), L.ptr(scratch3[1]),
-                                          L.ptr(scratch3[2]), L.ptr(rmask), L.stream_ptr(dev)),
-                "pnr_query_compact")
-        weight = torch.empty((1, Rv, SR, K), **f32)
-        blend = torch.empty((1, Rv, SR, 1), **f32)
-        op = opacity.detach().contiguous()
-        L.check(L.lib().pnr_march_aux(L.ctypes.byref(rays), L.ctypes.byref(qp), L.ctypes.byref(bufs.c),
-                                      L.ptr(xyz), L.ptr(op), Rv, L.ptr(weight), L.ptr(blend), L.stream_ptr(dev)),
-                "pnr_march_aux")
-        aux = {"weight": weight, "blend_weight": blend, "sample_pidx": pidx, "conf_coefficient": 1}
-        if np_.points_conf is not None:
-            cf = np_.points_conf.reshape(-1)[pidx.clamp(min=0).long()]
-            aux["conf_coefficient"] = cf - (cf - torch.clamp(cf, 1e-4, 1.0)).detach()
-        return aux
 
     @torch.no_grad()
     def eval_aux(self, campos, camrot, raydir, near, far, opacity):
@@ -650,7 +492,7 @@ class NeuralPointsRayMarching(nn.Module):
         xyz = np_.xyz.detach().contiguous()
         bufs, hp, rays, qp = np_.querier.run(xyz, raydir.float().contiguous(), cp, cr, near, far, bufs=None)
         cnt = bufs.read_counts()
-        return self._march_aux(rays, qp, bufs, raydir.shape[0], cnt["R_valid"], xyz, opacity)
+        return march_aux(self, rays, qp, bufs, raydir.shape[0], cnt["R_valid"], xyz, opacity)
 
     @torch.no_grad()
     def probe_maps(self, campos, camrot, raydir, near, far, opacity):

@@ -14,8 +14,6 @@ survivor's view and samples it.  One host read: the survivor count.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib as L
@@ -58,9 +56,7 @@ def seed_mask(xyz: torch.Tensor, frames: FrameSet, bits=None, ranges=None, near_
     box and every view, in input order."""
     n = xyz.shape[0]
     dev = xyz.device
-    nb = L.c_size_t(0)
-    L.check(L.lib().pnr_seed_scratch_bytes(n, ctypes.byref(nb)), "pnr_seed_scratch_bytes")
-    scratch = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+    scratch = L.scratch("pnr_seed_scratch_bytes", n, device=dev)
     keep = torch.empty(n, dtype=torch.int32, device=dev)
     src = torch.empty(n, dtype=torch.int32, device=dev)
     count = torch.zeros(1, dtype=torch.int32, device=dev)

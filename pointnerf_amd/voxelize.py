@@ -30,9 +30,7 @@ def construct_vox_points_closest(xyz_val: torch.Tensor, vox_res: int, partition_
     if n == 0:
         raise L.PnrError("construct_vox_points_closest: empty point cloud")
     dev = xyz.device
-    nb = L.c_size_t(0)
-    L.check(L.lib().pnr_vox_closest_scratch_bytes(n, L.ctypes.byref(nb)), "pnr_vox_closest_scratch_bytes")
-    scratch = torch.empty((int(nb.value) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+    scratch = L.scratch("pnr_vox_closest_scratch_bytes", n, device=dev)
     centroid = torch.empty((n, 3), dtype=torch.float32, device=dev)
     grid = torch.empty((n, 3), dtype=torch.int32, device=dev)
     min_idx = torch.empty(n, dtype=torch.int64, device=dev)

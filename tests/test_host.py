@@ -160,3 +160,22 @@ def test_grid_handle_finaliser_defers_destroy():
     finally:
         Q._CAPTURES[0] -= 1
         Q._DEFERRED.pop()
+
+
+def test_agg_spec_refuses_pair_mask_with_split_precision():
+    """A pair mask runs the fp32 masked forward only: AggSpec refuses it with a split
+    precision (it used to run the fp32 forward and then a split backward), and an
+    unknown precision; the seam's own combination, mask + fp32, constructs."""
+    import pytest
+    from pointnerf_amd import _lib as L
+    from pointnerf_amd.train import AggSpec, PointTables
+    mask = torch.ones(16, dtype=torch.uint8)
+    points = PointTables(torch.zeros(16, 3))
+    spec = AggSpec(None, L.Samples(), 2, points, pair_mask=mask)
+    assert spec.precision == "fp32" and spec.saved is None and spec.h2_fallback is False
+    for precision in ("fp32x3", "fp32h2"):
+        assert AggSpec(None, L.Samples(), 2, points, precision=precision).pair_mask is None
+        with pytest.raises(L.PnrError, match="pair mask"):
+            AggSpec(None, L.Samples(), 2, points, pair_mask=mask, precision=precision)
+    with pytest.raises(L.PnrError, match="precision"):
+        AggSpec(None, L.Samples(), 2, points, precision="bf16")

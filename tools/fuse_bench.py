@@ -152,9 +152,7 @@ def main():
 
     # the entry points on their own, with preallocated outputs
     n = F * H * W
-    nb = L.c_size_t(0)
-    L.check(L.lib().pnr_depth_fuse_scratch_bytes(F, H, W, ctypes.byref(nb)), "pnr_depth_fuse_scratch_bytes")
-    scratch = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+    scratch = L.scratch("pnr_depth_fuse_scratch_bytes", F, H, W, device=dev)
     keep, src = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
     total = torch.zeros(1, dtype=torch.int32, device=dev)
     prm = FU.fuse_params()
