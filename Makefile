@@ -14,6 +14,9 @@ build/%.o: $(SRC_DIR)/%.hip $(SRC_DIR)/pnr_common.h $(SRC_DIR)/agg_common.h $(SR
            include/pnr.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+# the handle and its tables: the grid build, the query and the handle's lifetime only
+# (prerequisites added after the pattern rule's, so $< stays the .hip)
+build/grid.o build/query.o build/api.o: $(SRC_DIR)/grid_tables.h
 
 # The query kernels must round exactly like the reference's fp32 ops: no FMA contraction.
 build/query.o build/grid.o build/voxelize.o: HIPFLAGS += -ffp-contract=off

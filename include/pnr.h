@@ -121,7 +121,14 @@ typedef struct {
  * are reallocated only when dims/max_o/P grow; grids up to 2^36 cells (int64
  * cell indices).  No host sync: the build counters travel to pinned host memory
  * behind an event that only pnr_grid_stats_get waits on.  Returns PNR_OK on
- * overflow; inspect pnr_grid_stats. */
+ * overflow; inspect pnr_grid_stats.
+ * A refused build (PNR_EINVAL: every argument is checked before anything is
+ * allocated or launched) leaves the handle and its grid as they were.  A build
+ * that fails after its checks (PNR_ENOMEM, PNR_EHIP) leaves the handle NOT
+ * built, whatever it held before: until the next successful build pnr_query,
+ * pnr_grid_export, pnr_grid_stats_get, pnr_grid_geometry and pnr_grid_bbox
+ * refuse with their "not built" messages.  The same holds for
+ * pnr_grid_build_dev. */
 int pnr_grid_build(pnr_handle* h, const float* xyz_dev, int64_t n,
                    const pnr_grid_params* p, void* stream);
 
@@ -162,6 +169,9 @@ typedef struct {
   int32_t dims[3];
 } pnr_grid_stats;
 int pnr_grid_stats_get(pnr_handle* h, pnr_grid_stats* out); /* waits for the last build */
+/* (querier.GridHandle.stats() adds table_bytes_est = dims' cells x 14.640625 B: the
+ * per-cell tables as the build allocates them -- three int32 cell tables, 84 B per
+ * 32-cell word, 4 B of coarse map per 256 cells; csrc/grid_tables.h GridLayout.) */
 
 /* Copy the grid tables out (inspection / parity tests; any pointer may be NULL):
  * coor_2_occ[gvol] (-1 empty), occ_bits[ceil(gvol/32)] dilated occupancy

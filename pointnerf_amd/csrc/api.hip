@@ -1,7 +1,7 @@
 // Handle lifetime, error reporting and ABI version of libpnr.so.
 #include <cstdarg>
 
-#include "pnr_common.h"
+#include "grid_tables.h"
 
 namespace pnr {
 

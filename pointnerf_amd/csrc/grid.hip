@@ -25,7 +25,7 @@
 // smallest key, found by an 8-pass radix select on the device (no host sync),
 // and per voxel the P points of smallest key.  Without overflow the tables
 // are exactly the serial order.
-#include "pnr_common.h"
+#include "grid_tables.h"
 
 namespace pnr {
 
@@ -163,8 +163,6 @@ __global__ void k_bbox_acc_init(unsigned* acc) {
   if (threadIdx.x < 3) acc[threadIdx.x] = 0xffffffffu;
   else if (threadIdx.x < 8) acc[threadIdx.x] = 0u;
 }
-
-__device__ __forceinline__ void grid_geom_from(const float* bb, const pnr_grid_spec& sp, QGrid* geo);
 
 __global__ void k_geom_acc(unsigned* acc, float* __restrict__ out6, pnr_grid_spec sp, QGrid* __restrict__ geo) {
   if (threadIdx.x != 0) return;
@@ -952,7 +950,6 @@ __global__ void __launch_bounds__(kBlock) k_rank_slots(int n_slots, GridDev g0, 
   }
 }
 
-// 16 lanes per rank: a voxel's records are one contiguous read and write
 // The build's statistics for the host (counters, the device geometry, the bbox
 // it came from) written by block 0 of the build's last kernel straight into the
 // handle's pinned host buffers (three hipMemcpyAsync before: ~15 us of the build).
@@ -965,6 +962,7 @@ struct HostStats {
   float* h_bbox;
 };
 
+// 16 lanes per rank: a voxel's records are one contiguous read and write
 __global__ void __launch_bounds__(kBlock) k_fill_recs(GridDev g, const int32_t* __restrict__ n_ranks,
                                                       const int32_t* __restrict__ rank_slot,
                                                       const int32_t* __restrict__ rec_off,
@@ -990,6 +988,8 @@ __global__ void __launch_bounds__(kBlock) k_fill_recs(GridDev g, const int32_t* 
 
 using namespace pnr;
 
+static_assert(sizeof(SelState) == kSelStateWords * 4, "pnr_handle::sel_hist() starts behind SelState");
+
 extern "C" int pnr_points_bbox(const float* xyz_dev, int64_t n, float* out6_dev, void* stream) {
   PNR_CHECK_ARG(xyz_dev && out6_dev, "bbox: null pointer");
   PNR_CHECK_ARG(n > 0, "bbox: empty point set");
@@ -1004,25 +1004,113 @@ extern "C" int pnr_points_bbox(const float* xyz_dev, int64_t n, float* out6_dev,
   return PNR_OK;
 }
 
-// bytes of the KNN's coarse column map for allocation bounds dims (16-B padded)
-static size_t coarse_bytes(const int dims[3]) {
-  return (((size_t)cdiv(dims[2], 8) * dims[0] * cdiv(dims[1], 32) * 4) + 15) & ~(size_t)15;
+// ------------------------------------------------------------------ layout
+GridLayout GridLayout::make(const int dims[3], int64_t max_o, int P, int64_t n, bool device_geometry) {
+  GridLayout L;
+  L.gvol = (int64_t)dims[0] * dims[1] * dims[2];
+  L.words = cdiv(L.gvol, 32);
+  L.cap_o = max_o;
+  L.n = n;
+  L.wide = L.gvol >= ((int64_t)1 << 32) - 1;   // the sentinel key gvol must fit the key type
+  const size_t gvol = (size_t)L.gvol, words = (size_t)L.words, cap_o = (size_t)max_o, np = (size_t)n;
+  // the KNN's coarse column map for the allocation bound, 16-B padded
+  const size_t coarse = (((size_t)cdiv(dims[2], 8) * dims[0] * cdiv(dims[1], 32) * 4) + 15) & ~(size_t)15;
+  L.occ_off = 0;
+  L.held_off = words * 32;
+  L.coarse_off = words * 64;
+  L.wrank_off = L.coarse_off + coarse;
+  L.clear_bytes = L.wrank_off;
+  L.wrank_cap = L.words + 4;
+  const int64_t hist_n = (int64_t)256 * cdiv(n, kRsTile) + 1;
+  int64_t scan_n = n;
+  for (int64_t m : {L.cap_o, L.words, hist_n}) scan_n = m > scan_n ? m : scan_n;
+  size_t* b = L.bytes;
+  b[GB_COOR_2_OCC] = b[GB_CELL_START] = b[GB_CELL_END] = gvol * 4;
+  b[GB_OCC_BITS] = words * 4;
+  b[GB_CELL_BYTES] = L.wrank_off + (size_t)L.wrank_cap * 4;
+  b[GB_OCC_NUMPNTS] = cap_o * 4;
+  b[GB_OCC_PTS] = cap_o * P * sizeof(float4);
+  b[GB_OCC_2_COOR] = cap_o * 12;
+  b[GB_SORT_K0] = b[GB_SORT_K1] = np * (L.wide ? 8 : 4);
+  b[GB_SORT_V0] = b[GB_SORT_V1] = b[GB_PT_FLAG] = np * 4;
+  b[GB_SORT_HIST] = b[GB_SORT_OFFS] = (size_t)hist_n * 4;
+  b[GB_PT_SLOT] = (np + 1) * 4;
+  b[GB_COUNTERS] = 8 * 4;
+  b[GB_SEL] = sizeof(SelState) + kSelPasses * 256 * 4;
+  b[GB_SCAN_TMP] = scan_scratch_bytes(scan_n);
+  b[GB_Q_WORDS] = words * 8;
+  b[GB_Q_WCNT] = (words + 1) * 4;
+  b[GB_Q_RANK_SLOT] = b[GB_Q_RANK_CNT] = cap_o * 4;
+  b[GB_Q_REC_OFF] = (cap_o + 1) * 4;
+  b[GB_Q_RECS] = np * sizeof(float4);
+  b[GB_GEOM] = sizeof(QGrid);
+  b[GB_BBOX] = device_geometry ? 8 * sizeof(float) : 0;
+  b[GB_BBOX_ACC] = device_geometry ? 8 * sizeof(unsigned) : 0;
+  return L;
 }
 
-// Sort, claim, count and fill (K: the cell key type, uint32 unless the grid
-// has 2^32 - 1 cells or more).
+// ------------------------------------------------------------------- build
+// One build, as both entry points state it.
+struct GridBuild {
+  const char* who;             // the entry point, for its messages
+  const float* xyz;
+  int64_t n;
+  const pnr_grid_spec* spec;   // set: the exact geometry is derived on the device from the points' bbox
+  QGrid geo;                   // spec == NULL: the exact geometry; else its bound (the ranges box: origin, dims_max).
+  int qs[3];                   //   geo.dims is the allocation bound either way, geo.P is P
+  int max_o, slot0_drop;
+  uint64_t seed;
+};
+
+struct BuildCtx {
+  pnr_handle* h;
+  const GridBuild& b;
+  GridDev g;        // the kernels' by-value parameters (they read the geometry itself from GB_GEOM)
+  hipStream_t st;
+  int cur;          // GB_SORT_K0 / GB_SORT_V0 + cur hold the sorted keys and ids (set by stage_sort)
+  const GridLayout& lay() const { return h->lay; }
+  // exclusive_scan into table `out` of the handle (capacity: the layout's), on the build's scratch
+  int scan(const int32_t* in, int64_t n, const int32_t* n_dev, GridBuf out, int32_t* total_dev,
+           const int32_t* run_if = nullptr) const {
+    return exclusive_scan(in, n, n_dev, h->tab<int32_t>(out), (int64_t)(lay().bytes[out] / 4), total_dev,
+                          h->buf[GB_SCAN_TMP].p, lay().bytes[GB_SCAN_TMP], st, 0, run_if);
+  }
+};
+
+// Geometry into GB_GEOM: the host's, or bbox -> get_hyperparameters on the device.
+static int stage_geometry(BuildCtx& c) {
+  pnr_handle* h = c.h;
+  QGrid* geo = h->tab<QGrid>(GB_GEOM);
+  if (!c.b.spec) {
+    hipLaunchKernelGGL(k_set_geom, dim3(1), dim3(64), 0, c.st, c.b.geo, geo);
+    PNR_LAUNCH_CHECK();
+    return PNR_OK;
+  }
+  unsigned* acc = h->tab<unsigned>(GB_BBOX_ACC);
+  if (!h->bbox_acc_ready) {   // the accumulators' initial state (each build's k_geom_acc restores it)
+    hipLaunchKernelGGL(k_bbox_acc_init, dim3(1), dim3(64), 0, c.st, acc);
+    PNR_LAUNCH_CHECK();
+    h->bbox_acc_ready = true;
+  }
+  hipLaunchKernelGGL(k_bbox, dim3(grid_for(cdiv(c.b.n, 4), kBlock, 512)), dim3(kBlock), 0, c.st, c.b.xyz, c.b.n, acc);
+  PNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_geom_acc, dim3(1), dim3(64), 0, c.st, acc, h->tab<float>(GB_BBOX), *c.b.spec, geo);
+  PNR_LAUNCH_CHECK();
+  return PNR_OK;
+}
+
+// (cell, point id) sorted by cell, ids ascending inside a cell (K: the cell key
+// type, uint32 unless the grid has 2^32 - 1 cells or more).  k_cell_keys also
+// clears pt_flag, the slot tables and the counters.
 template <typename K>
-static int build_tables(pnr_handle* h, const float* xyz_dev, int64_t n, const GridDev& g, int64_t gvol,
-                        int64_t words, int64_t cap_o, hipStream_t st) {
+static int stage_sort(BuildCtx& c) {
+  pnr_handle* h = c.h;
+  const GridLayout& L = c.lay();
+  hipStream_t st = c.st;
   int rc;
-  const QGrid* geo = h->geom.as<QGrid>();
-  int32_t* counters = h->counters.as<int32_t>();
-  int32_t* pt_flag = h->pt_flag.as<int32_t>();
-  int32_t* pt_slot = h->pt_slot.as<int32_t>();
-  int32_t* cell_start = h->cell_start.as<int32_t>();
-  int32_t* cell_end = h->cell_end.as<int32_t>();
-  const K sentinel = (K)gvol;
-  const int bits = 64 - __builtin_clzll((unsigned long long)gvol);
+  const int64_t n = L.n;
+  const K sentinel = (K)L.gvol;
+  const int bits = 64 - __builtin_clzll((unsigned long long)L.gvol);
   // 8-bit digits (kRB): 9-bit ones save c5's fourth pass (26-bit keys) but each
   // scatter pass took 185 instead of 120 us (4 keys per digit run of a tile:
   // partial lines) and the build 3.04 vs 2.79 ms (round 6)
@@ -1030,190 +1118,219 @@ static int build_tables(pnr_handle* h, const float* xyz_dev, int64_t n, const Gr
   const int rbits = kRB;
   const int passes = (bits + rbits - 1) / rbits;
   const int tiles = (int)cdiv(n, kRsTile);
-  const unsigned gp = grid_for(n, kBlock);
-
-  // (cell, point id) sorted by cell, ids ascending inside a cell
-  K* keys[2] = {h->sort_k[0].as<K>(), h->sort_k[1].as<K>()};
-  int32_t* vals[2] = {h->sort_v[0].as<int32_t>(), h->sort_v[1].as<int32_t>()};
-  const int64_t kblocks = cdiv(n > cap_o ? n : cap_o, kRsTile);
-  PNR_CHECK_ARG(kblocks < (int64_t)1 << 31, "grid_build: too many sort tiles");
+  int32_t* hist = h->tab<int32_t>(GB_SORT_HIST);
+  K* keys[2] = {h->tab<K>(GB_SORT_K0), h->tab<K>(GB_SORT_K1)};
+  int32_t* vals[2] = {h->tab<int32_t>(GB_SORT_V0), h->tab<int32_t>(GB_SORT_V1)};
+  PNR_HIP(hipMemsetAsync(h->buf[GB_COOR_2_OCC].p, 0xff, (size_t)L.gvol * 4, st));
+  const int64_t kblocks = cdiv(n > L.cap_o ? n : L.cap_o, kRsTile);   // < 2^20: n and max_o are int32
   hipLaunchKernelGGL((k_cell_keys<kRB, K>), dim3((unsigned)kblocks), dim3(kBlock), 0, st,
-                     xyz_dev, n, g, geo, sentinel, keys[0], cap_o, pt_flag, h->occ_numpnts.as<int32_t>(),
-                     h->occ_2_coor.as<int32_t>(), counters, tiles, h->sort_hist.as<int32_t>(),
-                     n > cap_o ? reinterpret_cast<uint32_t*>(h->sel.as<SelState>() + 1) : nullptr);
+                     c.b.xyz, n, c.g, h->tab<QGrid>(GB_GEOM), sentinel, keys[0], L.cap_o, h->tab<int32_t>(GB_PT_FLAG),
+                     h->tab<int32_t>(GB_OCC_NUMPNTS), h->tab<int32_t>(GB_OCC_2_COOR), h->tab<int32_t>(GB_COUNTERS),
+                     tiles, hist, n > L.cap_o ? h->sel_hist() : nullptr);
   PNR_LAUNCH_CHECK();
   int cur = 0;
   for (int pass = 0; pass < passes; ++pass) {
     const int shift = rbits * pass;
     if (pass > 0) {   // (pass 0's histogram: k_cell_keys)
-      hipLaunchKernelGGL((k_rs_hist<kRB, K>), dim3(tiles), dim3(kBlock), 0, st, keys[cur], n,
-                         shift, tiles, h->sort_hist.as<int32_t>());
+      hipLaunchKernelGGL((k_rs_hist<kRB, K>), dim3(tiles), dim3(kBlock), 0, st, keys[cur], n, shift, tiles, hist);
       PNR_LAUNCH_CHECK();
     }
-    if ((rc = exclusive_scan(h->sort_hist.as<int32_t>(), ((int64_t)1 << rbits) * tiles, nullptr,
-                             h->sort_offs.as<int32_t>(), (int64_t)(h->sort_offs.bytes / 4), nullptr, h->scan_tmp.p,
-                             h->scan_tmp.bytes, st)))
-      return rc;
+    if ((rc = c.scan(hist, ((int64_t)1 << rbits) * tiles, nullptr, GB_SORT_OFFS, nullptr))) return rc;
     hipLaunchKernelGGL((k_rs_scatter<kRB, K>), dim3(tiles), dim3(kBlock), 0, st, keys[cur],
-                       pass ? vals[cur] : nullptr, n, shift, tiles, h->sort_offs.as<int32_t>(), keys[cur ^ 1],
+                       pass ? vals[cur] : nullptr, n, shift, tiles, h->tab<int32_t>(GB_SORT_OFFS), keys[cur ^ 1],
                        vals[cur ^ 1]);
     PNR_LAUNCH_CHECK();
     cur ^= 1;
   }
-  const K* skey = keys[cur];
-  const int32_t* sid = vals[cur];
-  hipLaunchKernelGGL(k_runs<K>, dim3(gp), dim3(kBlock), 0, st, skey, sid, n, sentinel, pt_flag, cell_start,
-                     cell_end, counters);
+  c.cur = cur;
+  return PNR_OK;
+}
+
+// The run of every occupied cell, and slot = rank of the claimer's point id
+// (the serial claim order); counters[0] = the occupied voxels.
+template <typename K>
+static int stage_runs(BuildCtx& c) {
+  pnr_handle* h = c.h;
+  const GridLayout& L = c.lay();
+  int32_t* pt_flag = h->tab<int32_t>(GB_PT_FLAG);
+  int32_t* counters = h->tab<int32_t>(GB_COUNTERS);
+  hipLaunchKernelGGL(k_runs<K>, dim3(grid_for(L.n, kBlock)), dim3(kBlock), 0, c.st, h->tab<K>(GB_SORT_K0 + c.cur),
+                     h->tab<int32_t>(GB_SORT_V0 + c.cur), L.n, (K)L.gvol, pt_flag, h->tab<int32_t>(GB_CELL_START),
+                     h->tab<int32_t>(GB_CELL_END), counters);
   PNR_LAUNCH_CHECK();
-  // slot = rank of the claimer's point id (the serial claim order)
-  if ((rc = exclusive_scan(pt_flag, n, nullptr, pt_slot, (int64_t)(h->pt_slot.bytes / 4), counters + 0, h->scan_tmp.p, h->scan_tmp.bytes, st)))
-    return rc;
-  if (n > cap_o) {
-    // more points than max_o: the occupied voxels may overflow it (counters[0]
-    // holds their number on the device); keep the reservoir's max_o of them
-    SelState* ss = h->sel.as<SelState>();
-    uint32_t* hist = reinterpret_cast<uint32_t*>(ss + 1);
-    const unsigned gs = grid_for(n, kBlock, 1024);
-    // the claimers listed by slot (pass 0) in sort_v[cur ^ 1]: free after the sort
-    int32_t* cids = vals[cur ^ 1];
-    // passes 1.. and the apply walk the claimer list (<= the occupied voxels): fewer blocks
-    const unsigned gl = grid_for(cap_o, kBlock, 256);
-    for (int pass = 0; pass < kSelPasses; ++pass) {
-      hipLaunchKernelGGL(k_sel_hist, dim3(pass ? gl : gs), dim3(kBlock), 0, st, n, pt_flag, pt_slot, cids,
-                         counters + 0, g.seed, pass, (int)cap_o, ss, hist);
-      PNR_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_sel_apply, dim3(gl), dim3(kBlock), 0, st, cids, counters + 0, g.seed, (int)cap_o, ss, hist,
-                       pt_flag);
-    PNR_LAUNCH_CHECK();
-    if ((rc = exclusive_scan(pt_flag, n, nullptr, pt_slot, (int64_t)(h->pt_slot.bytes / 4), counters + 6, h->scan_tmp.p, h->scan_tmp.bytes, st, 0,
-                             &ss->active)))
-      return rc;
-  }
-  // cell_bytes = [occupancy bytes | held bytes | coarse column map | word ranks]: the
-  // first three cleared by one memset
-  uint8_t* occ_bytes = h->cell_bytes.as<uint8_t>();
-  PNR_HIP(hipMemsetAsync(occ_bytes, 0, (size_t)words * 64 + coarse_bytes(g.dims), st));
-  hipLaunchKernelGGL(k_claim<K>, dim3(gp), dim3(kBlock), 0, st, xyz_dev, n, g, geo, skey, sid, sentinel, pt_flag,
-                     pt_slot, cell_start, cell_end, h->coor_2_occ.as<int32_t>(), h->occ_2_coor.as<int32_t>(),
-                     occ_bytes, occ_bytes + words * 32, reinterpret_cast<uint32_t*>(occ_bytes + words * 64),
-                     h->occ_numpnts.as<int32_t>(), h->occ_pts.as<float4>(), h->q_rank_slot.as<int32_t>(), counters);
-  PNR_LAUNCH_CHECK();
-  // q_rank_slot is scratch until the query index below: slot -> run start
-  hipLaunchKernelGGL(k_reservoir, dim3(grid_for(cap_o, kBlock)), dim3(kBlock), 0, st, (int)cap_o, g, xyz_dev, sid,
-                     h->occ_numpnts.as<int32_t>(), h->q_rank_slot.as<int32_t>(), h->occ_pts.as<float4>());
-  PNR_LAUNCH_CHECK();
-  {
-    // cell_end is dead after k_claim: its storage holds the zy-dilated bytes
-    uint8_t* zy = h->cell_end.as<uint8_t>();
-    const unsigned gr = grid_for((int64_t)g.dims[0] * g.dims[1] * 64, kBlock, 1 << 16);   // one wave per row
-    hipLaunchKernelGGL(k_dilate_zy, dim3(gr), dim3(kBlock), 0, st, g, geo, occ_bytes, zy);
-    PNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_dilate_x, dim3(gr), dim3(kBlock), 0, st, g, geo, zy, occ_bytes);
+  return c.scan(pt_flag, L.n, nullptr, GB_PT_SLOT, counters + 0);
+}
+
+// More points than max_o: the occupied voxels may overflow it (counters[0]
+// holds their number on the device); keep the reservoir's max_o of them.
+// Live: claimers() (listed by slot in pass 0) and sel_hist().
+static int stage_select(BuildCtx& c) {
+  pnr_handle* h = c.h;
+  const GridLayout& L = c.lay();
+  hipStream_t st = c.st;
+  int32_t* pt_flag = h->tab<int32_t>(GB_PT_FLAG);
+  int32_t* pt_slot = h->tab<int32_t>(GB_PT_SLOT);
+  int32_t* counters = h->tab<int32_t>(GB_COUNTERS);
+  SelState* ss = h->tab<SelState>(GB_SEL);
+  uint32_t* hist = h->sel_hist();
+  int32_t* cids = h->claimers(c.cur);
+  const unsigned gs = grid_for(L.n, kBlock, 1024);
+  // passes 1.. and the apply walk the claimer list (<= the occupied voxels): fewer blocks
+  const unsigned gl = grid_for(L.cap_o, kBlock, 256);
+  for (int pass = 0; pass < kSelPasses; ++pass) {
+    hipLaunchKernelGGL(k_sel_hist, dim3(pass ? gl : gs), dim3(kBlock), 0, st, L.n, pt_flag, pt_slot, cids,
+                       counters + 0, c.g.seed, pass, (int)L.cap_o, ss, hist);
     PNR_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_pack_bits, dim3(grid_for(words, kBlock)), dim3(kBlock), 0, st, occ_bytes, words,
-                     h->occ_bits.as<uint32_t>());
+  hipLaunchKernelGGL(k_sel_apply, dim3(gl), dim3(kBlock), 0, st, cids, counters + 0, c.g.seed, (int)L.cap_o, ss, hist,
+                     pt_flag);
+  PNR_LAUNCH_CHECK();
+  return c.scan(pt_flag, L.n, nullptr, GB_PT_SLOT, counters + 6, &ss->active);
+}
+
+// Slot tables, occupancy / held bytes and the coarse map (k_claim), then the
+// per-voxel point reservoir.  Live from k_claim to k_reservoir: run_starts().
+template <typename K>
+static int stage_claim(BuildCtx& c) {
+  pnr_handle* h = c.h;
+  const GridLayout& L = c.lay();
+  hipStream_t st = c.st;
+  const int32_t* sid = h->tab<int32_t>(GB_SORT_V0 + c.cur);
+  PNR_HIP(hipMemsetAsync(h->cell_bytes(0), 0, L.clear_bytes, st));
+  hipLaunchKernelGGL(k_claim<K>, dim3(grid_for(L.n, kBlock)), dim3(kBlock), 0, st, c.b.xyz, L.n, c.g,
+                     h->tab<QGrid>(GB_GEOM), h->tab<K>(GB_SORT_K0 + c.cur), sid, (K)L.gvol, h->tab<int32_t>(GB_PT_FLAG),
+                     h->tab<int32_t>(GB_PT_SLOT), h->tab<int32_t>(GB_CELL_START), h->tab<int32_t>(GB_CELL_END),
+                     h->tab<int32_t>(GB_COOR_2_OCC), h->tab<int32_t>(GB_OCC_2_COOR), h->cell_bytes(L.occ_off),
+                     h->cell_bytes(L.held_off), reinterpret_cast<uint32_t*>(h->cell_bytes(L.coarse_off)),
+                     h->tab<int32_t>(GB_OCC_NUMPNTS), h->tab<float4>(GB_OCC_PTS), h->run_starts(),
+                     h->tab<int32_t>(GB_COUNTERS));
+  PNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_reservoir, dim3(grid_for(L.cap_o, kBlock)), dim3(kBlock), 0, st, (int)L.cap_o, c.g, c.b.xyz, sid,
+                     h->tab<int32_t>(GB_OCC_NUMPNTS), h->run_starts(), h->tab<float4>(GB_OCC_PTS));
   PNR_LAUNCH_CHECK();
   return PNR_OK;
 }
 
-// The build proper (both entry points): p gives the allocation bounds (dims)
-// and the by-value parameters; the exact geometry is already in h->geom.
-static int grid_build_body(pnr_handle* h, const float* xyz_dev, int64_t n, const pnr_grid_params* p,
-                           hipStream_t st) {
-  PNR_CHECK_ARG(n > 0 && n < (int64_t)1 << 31, "grid_build: point count %lld out of range", (long long)n);
-  PNR_CHECK_ARG(p->dims[0] > 0 && p->dims[1] > 0 && p->dims[2] > 0, "grid_build: empty grid dims");
-  PNR_CHECK_ARG(p->max_o > 0 && p->P > 0, "grid_build: max_o and P must be > 0");
-  PNR_CHECK_ARG(p->vsize[0] > 0 && p->vsize[1] > 0 && p->vsize[2] > 0, "grid_build: vsize <= 0");
-  const int64_t gvol = (int64_t)p->dims[0] * p->dims[1] * p->dims[2];
-  PNR_CHECK_ARG(gvol < (int64_t)1 << 36, "grid_build: grid of %lld cells", (long long)gvol);
+// The occupancy bytes dilated by query_size and packed into GB_OCC_BITS.
+// Live between the two dilation kernels: zy_bytes().
+static int stage_dilate(BuildCtx& c) {
+  pnr_handle* h = c.h;
+  const GridLayout& L = c.lay();
+  const QGrid* geo = h->tab<QGrid>(GB_GEOM);
+  uint8_t* occ_bytes = h->cell_bytes(L.occ_off);
+  const unsigned gr = grid_for((int64_t)c.g.dims[0] * c.g.dims[1] * 64, kBlock, 1 << 16);   // one wave per row
+  hipLaunchKernelGGL(k_dilate_zy, dim3(gr), dim3(kBlock), 0, c.st, c.g, geo, occ_bytes, h->zy_bytes());
+  PNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_dilate_x, dim3(gr), dim3(kBlock), 0, c.st, c.g, geo, h->zy_bytes(), occ_bytes);
+  PNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_pack_bits, dim3(grid_for(L.words, kBlock)), dim3(kBlock), 0, c.st, occ_bytes, L.words,
+                     h->tab<uint32_t>(GB_OCC_BITS));
+  PNR_LAUNCH_CHECK();
+  return PNR_OK;
+}
+
+// Query index: held voxels ranked in cell order (k_knn's tables); counters[4] =
+// the ranks, counters[5] = the records.
+static int stage_query_index(BuildCtx& c) {
+  pnr_handle* h = c.h;
+  const GridLayout& L = c.lay();
+  hipStream_t st = c.st;
   int rc;
-  const int64_t words = cdiv(gvol, 32);
-  const int64_t cap_o = p->max_o;
-  const bool wide = gvol >= ((int64_t)1 << 32) - 1;   // the sentinel key gvol must fit the key type
-  const size_t kbytes = wide ? 8 : 4;
-  const int64_t hist_n = (int64_t)256 * cdiv(n, kRsTile) + 1;
-  int64_t scan_n = n;
-  for (int64_t m : {cap_o, words, hist_n}) scan_n = m > scan_n ? m : scan_n;
-  if ((rc = h->coor_2_occ.ensure(gvol * 4)) || (rc = h->cell_end.ensure(gvol * 4)) ||
-      (rc = h->cell_bytes.ensure(words * 68 + 16 + coarse_bytes(p->dims))) || (rc = h->occ_bits.ensure(words * 4)) ||
-      (rc = h->occ_numpnts.ensure(cap_o * 4)) || (rc = h->occ_pts.ensure(cap_o * p->P * sizeof(float4))) ||
-      (rc = h->occ_2_coor.ensure(cap_o * 12)) || (rc = h->sort_k[0].ensure(n * kbytes)) ||
-      (rc = h->sort_k[1].ensure(n * kbytes)) || (rc = h->sort_v[0].ensure(n * 4)) ||
-      (rc = h->sort_v[1].ensure(n * 4)) || (rc = h->sort_hist.ensure(hist_n * 4)) ||
-      (rc = h->sort_offs.ensure(hist_n * 4)) || (rc = h->cell_start.ensure(gvol * 4)) ||
-      (rc = h->pt_flag.ensure(n * 4)) || (rc = h->pt_slot.ensure((n + 1) * 4)) ||
-      (rc = h->counters.ensure(8 * 4)) || (rc = h->sel.ensure(sizeof(SelState) + kSelPasses * 256 * 4)) ||
-      (rc = h->scan_tmp.ensure(scan_scratch_bytes(scan_n))) ||
-      (rc = h->q_words.ensure(words * 8)) || (rc = h->q_wcnt.ensure((words + 1) * 4)) ||
-      (rc = h->q_rank_slot.ensure(cap_o * 4)) || (rc = h->q_rank_cnt.ensure(cap_o * 4)) ||
-      (rc = h->q_rec_off.ensure((cap_o + 1) * 4)) || (rc = h->q_recs.ensure(n * sizeof(float4))))
+  uint2* qw = h->tab<uint2>(GB_Q_WORDS);
+  int32_t* wcnt = h->tab<int32_t>(GB_Q_WCNT);
+  int32_t* wrank = reinterpret_cast<int32_t*>(h->cell_bytes(L.wrank_off));
+  int32_t* counters = h->tab<int32_t>(GB_COUNTERS);
+  hipLaunchKernelGGL(k_pack_held, dim3(grid_for(L.words, kBlock)), dim3(kBlock), 0, st, h->cell_bytes(L.held_off),
+                     L.words, qw, wcnt);
+  PNR_LAUNCH_CHECK();
+  if ((rc = exclusive_scan(wcnt, L.words, nullptr, wrank, L.wrank_cap, counters + 4, h->buf[GB_SCAN_TMP].p,
+                           L.bytes[GB_SCAN_TMP], st)))
     return rc;
-  int32_t* occ_numpnts = h->occ_numpnts.as<int32_t>();
-  int32_t* occ_2_coor = h->occ_2_coor.as<int32_t>();
-  int32_t* counters = h->counters.as<int32_t>();
-  const QGrid* geo = h->geom.as<QGrid>();
+  hipLaunchKernelGGL(k_word_rank, dim3(grid_for(L.words, kBlock)), dim3(kBlock), 0, st, L.words, wrank, qw);
+  PNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_rank_slots, dim3(grid_for(L.cap_o, kBlock)), dim3(kBlock), 0, st, (int)L.cap_o, c.g,
+                     h->tab<QGrid>(GB_GEOM), h->tab<int32_t>(GB_OCC_NUMPNTS), h->tab<int32_t>(GB_OCC_2_COOR), qw,
+                     h->tab<int32_t>(GB_Q_RANK_SLOT), h->tab<int32_t>(GB_Q_RANK_CNT));
+  PNR_LAUNCH_CHECK();
+  return c.scan(h->tab<int32_t>(GB_Q_RANK_CNT), L.cap_o, counters + 4, GB_Q_REC_OFF, counters + 5);
+}
 
-  GridDev g;
-  for (int a = 0; a < 3; ++a) {
-    g.shift[a] = p->shift[a];
-    g.vs[a] = p->vsize[a];
-    g.dims[a] = p->dims[a];
-    g.qs[a] = p->query_size[a];
-  }
-  g.max_o = p->max_o;
-  g.P = p->P;
-  g.slot0_drop = p->slot0_drop;
-  g.seed = p->seed;
-
-  // (pt_flag, the slot tables and the counters are cleared by k_cell_keys)
-  PNR_HIP(hipMemsetAsync(h->coor_2_occ.p, 0xff, (size_t)gvol * 4, st));
-  if ((rc = wide ? build_tables<uint64_t>(h, xyz_dev, n, g, gvol, words, cap_o, st)
-                 : build_tables<uint32_t>(h, xyz_dev, n, g, gvol, words, cap_o, st)))
-    return rc;
-  float4* occ_pts = h->occ_pts.as<float4>();
-  uint8_t* occ_bytes = h->cell_bytes.as<uint8_t>();
-  // query index: held voxels ranked in cell order (k_knn's tables)
-  {
-    uint2* qw = h->q_words.as<uint2>();
-    int32_t* wcnt = h->q_wcnt.as<int32_t>();
-    const uint8_t* held_bytes = occ_bytes + words * 32;                    // written by k_claim
-    const size_t cb = coarse_bytes(p->dims);
-    h->coarse_off = (size_t)words * 64;   // the KNN reads the coarse map there (query.hip)
-    int32_t* wrank = reinterpret_cast<int32_t*>(occ_bytes + words * 64 + cb);   // after the maps
-    hipLaunchKernelGGL(k_pack_held, dim3(grid_for(words, kBlock)), dim3(kBlock), 0, st, held_bytes, words, qw, wcnt);
-    PNR_LAUNCH_CHECK();
-    if ((rc = exclusive_scan(wcnt, words, nullptr, wrank, (int64_t)((h->cell_bytes.bytes - words * 64 - cb) / 4), counters + 4, h->scan_tmp.p, h->scan_tmp.bytes, st)))
-      return rc;
-    hipLaunchKernelGGL(k_word_rank, dim3(grid_for(words, kBlock)), dim3(kBlock), 0, st, words, wrank, qw);
-    PNR_LAUNCH_CHECK();
-
-    hipLaunchKernelGGL(k_rank_slots, dim3(grid_for(cap_o, kBlock)), dim3(kBlock), 0, st, (int)cap_o, g, geo,
-                       occ_numpnts, occ_2_coor, qw, h->q_rank_slot.as<int32_t>(), h->q_rank_cnt.as<int32_t>());
-    PNR_LAUNCH_CHECK();
-    if ((rc = exclusive_scan(h->q_rank_cnt.as<int32_t>(), cap_o, counters + 4, h->q_rec_off.as<int32_t>(),
-                             (int64_t)(h->q_rec_off.bytes / 4), counters + 5, h->scan_tmp.p, h->scan_tmp.bytes, st)))
-      return rc;
-    if (!h->host_cnt) PNR_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->host_cnt), 8 * sizeof(int32_t)));
-    if (!h->host_geom) PNR_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->host_geom), sizeof(QGrid)));
-    if (h->geom_on_device && !h->host_bbox)
-      PNR_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->host_bbox), 8 * sizeof(float)));
-    if (!h->stats_ev) PNR_HIP(hipEventCreateWithFlags(&h->stats_ev, hipEventDisableTiming));
-    if (h->stats_pending) PNR_HIP(hipEventSynchronize(h->stats_ev));   // the previous build's stats are written
-    // (the bbox: of a device-geometry build, the one its geometry came from -- pnr_grid_bbox)
-    const HostStats hs = {counters, geo, h->geom_on_device ? h->bbox.as<float>() : nullptr, h->host_cnt, h->host_geom,
-                          h->host_bbox};
-    hipLaunchKernelGGL(k_fill_recs, dim3(grid_for(cap_o * 16, kBlock)), dim3(kBlock), 0, st, g, counters + 4,
-                       h->q_rank_slot.as<int32_t>(), h->q_rec_off.as<int32_t>(), occ_pts, h->q_recs.as<float4>(), hs);
-    PNR_LAUNCH_CHECK();
-  }
-  PNR_HIP(hipEventRecord(h->stats_ev, st));
+// The records in rank order, and with them (block 0 of the build's last kernel)
+// the counters, the exact geometry and the bbox into the pinned block; the
+// event that says they are there.
+static int stage_stats(BuildCtx& c) {
+  pnr_handle* h = c.h;
+  const GridLayout& L = c.lay();
+  const int32_t* counters = h->tab<int32_t>(GB_COUNTERS);
+  if (h->stats_pending) PNR_HIP(hipEventSynchronize(h->stats_ev));   // the previous build's stats are written
+  // (the bbox: of a device-geometry build, the one its geometry came from -- pnr_grid_bbox)
+  const HostStats hs = {counters, h->tab<QGrid>(GB_GEOM), c.b.spec ? h->tab<float>(GB_BBOX) : nullptr, h->host->cnt,
+                        &h->host->geo, h->host->bbox};
+  hipLaunchKernelGGL(k_fill_recs, dim3(grid_for(L.cap_o * 16, kBlock)), dim3(kBlock), 0, c.st, c.g, counters + 4,
+                     h->tab<int32_t>(GB_Q_RANK_SLOT), h->tab<int32_t>(GB_Q_REC_OFF), h->tab<float4>(GB_OCC_PTS),
+                     h->tab<float4>(GB_Q_RECS), hs);
+  PNR_LAUNCH_CHECK();
+  PNR_HIP(hipEventRecord(h->stats_ev, c.st));
   h->stats_pending = true;
-  h->gp = *p;
-  h->gvol = gvol;
-  h->n_points = n;
-  for (int a = 0; a < 3; ++a) h->stats.dims[a] = p->dims[a];
+  return PNR_OK;
+}
+
+template <typename K>
+static int build_stages(BuildCtx& c) {
+  int rc;
+  if ((rc = stage_geometry(c)) || (rc = stage_sort<K>(c)) || (rc = stage_runs<K>(c))) return rc;
+  if (c.lay().n > c.lay().cap_o && (rc = stage_select(c))) return rc;
+  if ((rc = stage_claim<K>(c)) || (rc = stage_dilate(c)) || (rc = stage_query_index(c)) || (rc = stage_stats(c)))
+    return rc;
+  return PNR_OK;
+}
+
+// The build (both entry points).  Every argument check comes before anything
+// is touched; from there until the last launch succeeded the handle is not
+// built, so a build that fails half way (PNR_ENOMEM, PNR_EHIP) leaves a handle
+// that pnr_query / pnr_grid_export / pnr_grid_stats_get / pnr_grid_geometry /
+// pnr_grid_bbox refuse.
+static int grid_build(pnr_handle* h, const GridBuild& b, hipStream_t st) {
+  PNR_CHECK_ARG(b.n > 0 && b.n < (int64_t)1 << 31, "%s: point count %lld out of range", b.who, (long long)b.n);
+  if (b.spec)
+    for (int a = 0; a < 3; ++a) {
+      PNR_CHECK_ARG(b.spec->ranges[a] < b.spec->ranges[3 + a], "grid_build_dev: needs ranges (min < max)");
+      PNR_CHECK_ARG(b.spec->dims_max[a] > 0 && b.spec->vsize[a] > 0 && b.spec->vscale[a] > 0 &&
+                        b.spec->vsize_s[a] > 0,
+                    "grid_build_dev: bad spec");
+    }
+  const QGrid& G = b.geo;
+  PNR_CHECK_ARG(G.dims[0] > 0 && G.dims[1] > 0 && G.dims[2] > 0, "grid_build: empty grid dims");
+  PNR_CHECK_ARG(b.max_o > 0 && G.P > 0, "grid_build: max_o and P must be > 0");
+  PNR_CHECK_ARG(G.vs[0] > 0 && G.vs[1] > 0 && G.vs[2] > 0, "grid_build: vsize <= 0");
+  const int64_t gvol = (int64_t)G.dims[0] * G.dims[1] * G.dims[2];
+  PNR_CHECK_ARG(gvol < (int64_t)1 << 36, "grid_build: grid of %lld cells", (long long)gvol);
+  PNR_HIP(hipSetDevice(h->device));
+
+  h->built = false;
+  h->lay = GridLayout::make(G.dims, b.max_o, G.P, b.n, b.spec != nullptr);
+  int rc;
+  for (int i = 0; i < kGridBufs; ++i)
+    if (h->lay.bytes[i] && (rc = h->buf[i].ensure(h->lay.bytes[i]))) return rc;
+  if (!h->host) PNR_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->host), sizeof(GridHostBlock)));
+  if (!h->stats_ev) PNR_HIP(hipEventCreateWithFlags(&h->stats_ev, hipEventDisableTiming));
+  for (int a = 0; a < 3; ++a) h->bound_dims[a] = G.dims[a];
+  h->max_o = b.max_o;
+  h->P = G.P;
+  h->geom_on_device = b.spec != nullptr;
+
+  BuildCtx c = {h, b, GridDev{}, st, 0};
+  for (int a = 0; a < 3; ++a) {
+    c.g.shift[a] = G.shift[a];
+    c.g.vs[a] = G.vs[a];
+    c.g.dims[a] = G.dims[a];
+    c.g.qs[a] = b.qs[a];
+  }
+  c.g.max_o = b.max_o;
+  c.g.P = G.P;
+  c.g.slot0_drop = b.slot0_drop;
+  c.g.seed = b.seed;
+  if ((rc = h->lay.wide ? build_stages<uint64_t>(c) : build_stages<uint32_t>(c))) return rc;
   h->built = true;
   return PNR_OK;
 }
@@ -1221,81 +1338,54 @@ static int grid_build_body(pnr_handle* h, const float* xyz_dev, int64_t n, const
 extern "C" int pnr_grid_build(pnr_handle* h, const float* xyz_dev, int64_t n,
                               const pnr_grid_params* p, void* stream) {
   PNR_CHECK_ARG(h && xyz_dev && p, "grid_build: null pointer");
-  PNR_HIP(hipSetDevice(h->device));
-  hipStream_t st = as_stream(stream);
-  int rc;
-  if ((rc = h->geom.ensure(sizeof(QGrid)))) return rc;
-  QGrid G;
+  GridBuild b = {"grid_build", xyz_dev, n, nullptr};
   for (int a = 0; a < 3; ++a) {
-    G.shift[a] = p->shift[a];
-    G.vs[a] = p->vsize[a];
-    G.dims[a] = p->dims[a];
+    b.geo.shift[a] = p->shift[a];
+    b.geo.vs[a] = p->vsize[a];
+    b.geo.dims[a] = p->dims[a];
+    b.qs[a] = p->query_size[a];
   }
-  G.P = p->P;
-  hipLaunchKernelGGL(k_set_geom, dim3(1), dim3(64), 0, st, G, h->geom.as<QGrid>());
-  PNR_LAUNCH_CHECK();
-  h->geom_on_device = false;
-  return grid_build_body(h, xyz_dev, n, p, st);
+  b.geo.P = p->P;
+  b.max_o = p->max_o;
+  b.slot0_drop = p->slot0_drop;
+  b.seed = p->seed;
+  return grid_build(h, b, as_stream(stream));
 }
 
 extern "C" int pnr_grid_build_dev(pnr_handle* h, const float* xyz_dev, int64_t n, const pnr_grid_spec* sp,
                                   void* stream) {
   PNR_CHECK_ARG(h && xyz_dev && sp, "grid_build_dev: null pointer");
-  PNR_CHECK_ARG(n > 0 && n < (int64_t)1 << 31, "grid_build_dev: point count %lld out of range", (long long)n);
+  GridBuild b = {"grid_build_dev", xyz_dev, n, sp};
   for (int a = 0; a < 3; ++a) {
-    PNR_CHECK_ARG(sp->ranges[a] < sp->ranges[3 + a], "grid_build_dev: needs ranges (min < max)");
-    PNR_CHECK_ARG(sp->dims_max[a] > 0 && sp->vsize[a] > 0 && sp->vscale[a] > 0 && sp->vsize_s[a] > 0,
-                  "grid_build_dev: bad spec");
+    b.geo.shift[a] = sp->ranges[a] - sp->pad[a];   // the ranges box: what the exact geometry cannot exceed
+    b.geo.vs[a] = sp->vsize_s[a];
+    b.geo.dims[a] = sp->dims_max[a];
+    b.qs[a] = sp->query_size[a];
   }
-  PNR_HIP(hipSetDevice(h->device));
-  hipStream_t st = as_stream(stream);
-  int rc;
-  const bool fresh = h->bbox_acc.p == nullptr;
-  if ((rc = h->geom.ensure(sizeof(QGrid))) || (rc = h->bbox.ensure(8 * sizeof(float))) ||
-      (rc = h->bbox_acc.ensure(8 * sizeof(unsigned))))
-    return rc;
-  if (fresh) {   // the accumulators' initial state (each build's last block restores it)
-    hipLaunchKernelGGL(k_bbox_acc_init, dim3(1), dim3(64), 0, st, h->bbox_acc.as<unsigned>());
-    PNR_LAUNCH_CHECK();
-  }
-  // bbox -> geometry on the device (get_hyperparameters)
-  hipLaunchKernelGGL(k_bbox, dim3(grid_for(cdiv(n, 4), kBlock, 512)), dim3(kBlock), 0, st, xyz_dev, n,
-                     h->bbox_acc.as<unsigned>());
-  PNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_geom_acc, dim3(1), dim3(64), 0, st, h->bbox_acc.as<unsigned>(), h->bbox.as<float>(), *sp,
-                     h->geom.as<QGrid>());
-  PNR_LAUNCH_CHECK();
-  pnr_grid_params p{};
-  for (int a = 0; a < 3; ++a) {
-    p.shift[a] = sp->ranges[a] - sp->pad[a];   // unused by the kernels (geometry from h->geom)
-    p.vsize[a] = sp->vsize_s[a];
-    p.dims[a] = sp->dims_max[a];
-    p.query_size[a] = sp->query_size[a];
-  }
-  p.max_o = sp->max_o;
-  p.P = sp->P;
-  p.slot0_drop = sp->slot0_drop;
-  p.seed = sp->seed;
-  h->geom_on_device = true;
-  return grid_build_body(h, xyz_dev, n, &p, st);
+  b.geo.P = sp->P;
+  b.max_o = sp->max_o;
+  b.slot0_drop = sp->slot0_drop;
+  b.seed = sp->seed;
+  return grid_build(h, b, as_stream(stream));
 }
 
 extern "C" int pnr_grid_bbox(pnr_handle* h, float out6[6]) {
   PNR_CHECK_ARG(h && out6, "grid_bbox: null pointer");
-  PNR_CHECK_ARG(h->built && h->geom_on_device && h->host_bbox, "grid_bbox: no device-geometry build");
+  PNR_CHECK_ARG(h->built && h->geom_on_device, "grid_bbox: no device-geometry build");
   PNR_HIP(hipEventSynchronize(h->stats_ev));
-  for (int a = 0; a < 6; ++a) out6[a] = h->host_bbox[a];
+  for (int a = 0; a < 6; ++a) out6[a] = h->host->bbox[a];
   return PNR_OK;
 }
 
 extern "C" int pnr_grid_geometry(pnr_handle* h, float shift[3], float vsize[3], int32_t dims[3]) {
-  PNR_CHECK_ARG(h && h->built && h->host_geom, "grid_geometry: grid not built");
+  PNR_CHECK_ARG(h && h->built, "grid_geometry: grid not built");
   PNR_CHECK_ARG(shift && vsize && dims, "grid_geometry: null pointer");
   PNR_HIP(hipEventSynchronize(h->stats_ev));
+  const QGrid& G = h->host->geo;
   for (int a = 0; a < 3; ++a) {
-    shift[a] = h->host_geom->shift[a];
-    vsize[a] = h->host_geom->vs[a];
-    dims[a] = h->host_geom->dims[a];
+    shift[a] = G.shift[a];
+    vsize[a] = G.vs[a];
+    dims[a] = G.dims[a];
   }
   return PNR_OK;
 }
@@ -1321,15 +1411,15 @@ extern "C" int pnr_grid_export(pnr_handle* h, int32_t* coor_2_occ, uint32_t* occ
   if ((rc = pnr_grid_geometry(h, sh, vs, dm))) return rc;
   const int64_t gvol = (int64_t)dm[0] * dm[1] * dm[2];
   const int64_t words = cdiv(gvol, 32);
-  const int64_t cap_o = h->gp.max_o;
+  const int64_t cap_o = h->max_o;
   if (coor_2_occ)
-    PNR_HIP(hipMemcpyAsync(coor_2_occ, h->coor_2_occ.p, gvol * 4, hipMemcpyDeviceToDevice, st));
-  if (occ_bits) PNR_HIP(hipMemcpyAsync(occ_bits, h->occ_bits.p, words * 4, hipMemcpyDeviceToDevice, st));
+    PNR_HIP(hipMemcpyAsync(coor_2_occ, h->buf[GB_COOR_2_OCC].p, gvol * 4, hipMemcpyDeviceToDevice, st));
+  if (occ_bits) PNR_HIP(hipMemcpyAsync(occ_bits, h->buf[GB_OCC_BITS].p, words * 4, hipMemcpyDeviceToDevice, st));
   if (occ_numpnts)
-    PNR_HIP(hipMemcpyAsync(occ_numpnts, h->occ_numpnts.p, cap_o * 4, hipMemcpyDeviceToDevice, st));
+    PNR_HIP(hipMemcpyAsync(occ_numpnts, h->buf[GB_OCC_NUMPNTS].p, cap_o * 4, hipMemcpyDeviceToDevice, st));
   if (occ_2_pnts) {
-    hipLaunchKernelGGL(k_export_ids, dim3(grid_for(cap_o * h->gp.P, kBlock)), dim3(kBlock), 0, st,
-                       (int)cap_o, h->gp.P, h->occ_numpnts.as<int32_t>(), h->occ_pts.as<float4>(),
+    hipLaunchKernelGGL(k_export_ids, dim3(grid_for(cap_o * h->P, kBlock)), dim3(kBlock), 0, st,
+                       (int)cap_o, h->P, h->tab<int32_t>(GB_OCC_NUMPNTS), h->tab<float4>(GB_OCC_PTS),
                        occ_2_pnts);
     PNR_LAUNCH_CHECK();
   }
@@ -1341,13 +1431,13 @@ extern "C" int pnr_grid_stats_get(pnr_handle* h, pnr_grid_stats* out) {
   PNR_CHECK_ARG(h->built, "grid_stats: grid not built");
   if (h->stats_pending) {
     PNR_HIP(hipEventSynchronize(h->stats_ev));
-    const int32_t* cnt = h->host_cnt;
+    const int32_t* cnt = h->host->cnt;
     h->stats.n_voxels = cnt[0];
-    h->stats.n_voxels_kept = cnt[0] < h->gp.max_o ? cnt[0] : h->gp.max_o;
+    h->stats.n_voxels_kept = cnt[0] < h->max_o ? cnt[0] : h->max_o;
     h->stats.n_points_in_grid = cnt[1];
     h->stats.n_points_dropped = cnt[2];
     h->stats.max_points_per_voxel = cnt[3];
-    for (int a = 0; a < 3; ++a) h->stats.dims[a] = h->host_geom->dims[a];
+    for (int a = 0; a < 3; ++a) h->stats.dims[a] = h->host->geo.dims[a];
     h->stats_pending = false;
   }
   *out = h->stats;

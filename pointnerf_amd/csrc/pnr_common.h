@@ -190,104 +190,3 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
 }
 
 }  // namespace pnr
-
-// A device allocation that only grows.
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  int ensure(size_t want) {
-    if (p && bytes >= want) return PNR_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    if (hipMalloc(&p, want ? want : 16) != hipSuccess) {
-      ::pnr::set_error("hipMalloc of %zu bytes failed", want);
-      return PNR_ENOMEM;
-    }
-    bytes = want;
-    return PNR_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-// Grid geometry as the build and query kernels read it from device memory
-// (pnr_handle.geom): written by the host (pnr_grid_build) or derived from the
-// points' bbox on the device (pnr_grid_build_dev, no host sync).
-struct QGrid {
-  float shift[3], vs[3];
-  int dims[3];
-  int P;
-};
-
-// Persistent grid tables owned by a handle (built by pnr_grid_build).
-struct pnr_handle {
-  int device = 0;
-  pnr_grid_params gp{};
-  int64_t gvol = 0;       // dims[0]*dims[1]*dims[2]
-  DevBuf coor_2_occ;      // int32 [gvol]   cell -> slot, -1 = empty
-  DevBuf occ_bits;        // uint32 [gvol/32] dilated occupancy bitmap
-  DevBuf cell_end;        // int32 [gvol]   one past the last sorted position of the cell's run (occupied cells only)
-  DevBuf cell_bytes;      // uint8 [32*words] x 2, the coarse column map, int32 [words+1]: occupancy bytes
-                          //   before packing, held bytes, the KNN's coarse map (uint32 [ceil(dz/8)][dx]
-                          //   [ceil(dy/32)]: bit y = column (x, y) holds a kept point in z-block bz), word ranks
-  size_t coarse_off = 0;  // byte offset of the coarse map in cell_bytes
-  DevBuf occ_numpnts;     // int32 [max_o]  points that fell in the voxel
-  DevBuf occ_pts;         // float4 [max_o*P] {x, y, z, bitcast(point id)}
-  DevBuf occ_2_coor;      // int32 [max_o*3]
-  DevBuf sort_k[2];       // uint32/uint64 [N] cell keys (ping-pong of the LSD radix sort)
-  DevBuf sort_v[2];       // int32 [N]      point ids riding with the keys
-  DevBuf sort_hist;       // int32 [256*tiles + 1] per-tile digit counts, then their exclusive scan
-  DevBuf sort_offs;       // int32 [256*tiles + 1]
-  DevBuf cell_start;      // int32 [gvol]   first sorted position of the cell's run (occupied cells only)
-  DevBuf pt_flag;         // int32 [N]
-  DevBuf pt_slot;         // int32 [N+1]
-  DevBuf counters;        // int32 [8]
-  DevBuf sel;             // voxel reservoir: radix-select state + 8 x 256-bin histograms
-  DevBuf scan_tmp;
-  // Query index (what k_knn reads; the slot tables above stay the reference's
-  // view for export / parity): the voxels that hold points, ranked in x-major
-  // cell order, so a sample's 3x3x3 neighbourhood is found from a bitmap that
-  // stays in L2 and its records sit near each other in HBM.
-  DevBuf q_words;         // uint2 [gvol/32] {bits: cell holds >= 1 kept point, rank of the word's first cell}
-  DevBuf q_wcnt;          // int32 [gvol/32] scratch: popcount per word
-  DevBuf q_rank_slot;     // int32 [max_o]   slot of rank r (scratch)
-  DevBuf q_rank_cnt;      // int32 [max_o]   min(P, points) of rank r (scratch)
-  DevBuf q_rec_off;       // int32 [max_o+1] first record of rank r (exclusive scan of q_rank_cnt)
-  DevBuf q_recs;          // float4 [N]      {x, y, z, bitcast(id)} in rank order, per voxel ascending id
-  DevBuf geom;            // QGrid of the built grid (device)
-  DevBuf bbox;            // float [8] point bbox of the last pnr_grid_build_dev
-  DevBuf bbox_acc;        // uint32 [8] k_bbox_geom's order-key accumulators + block ticket (kept reset)
-  QGrid* host_geom = nullptr;   // pinned copy of geom behind stats_ev
-  float* host_bbox = nullptr;   // pinned copy of bbox (device builds) behind stats_ev
-  bool geom_on_device = false;  // gp.shift / dims are bounds, the exact geometry is geom (device)
-  int64_t n_points = 0;
-  pnr_grid_stats stats{};
-  bool built = false;
-  // build counters read back without blocking the build: pinned copy + event,
-  // waited on by pnr_grid_stats_get only
-  int32_t* host_cnt = nullptr;
-  hipEvent_t stats_ev = nullptr;
-  bool stats_pending = false;
-  void release_all() {
-    if (host_cnt) (void)hipHostFree(host_cnt);
-    if (host_geom) (void)hipHostFree(host_geom);
-    host_geom = nullptr;
-    if (host_bbox) (void)hipHostFree(host_bbox);
-    host_bbox = nullptr;
-    if (stats_ev) (void)hipEventDestroy(stats_ev);
-    host_cnt = nullptr;
-    stats_ev = nullptr;
-    stats_pending = false;
-    DevBuf* all[] = {&coor_2_occ, &occ_bits, &cell_end, &cell_bytes, &occ_numpnts, &occ_pts, &occ_2_coor,
-                     &sort_k[0], &sort_k[1], &sort_v[0], &sort_v[1], &sort_hist, &sort_offs,
-                     &cell_start, &pt_flag, &pt_slot, &counters, &sel, &scan_tmp, &q_words, &q_wcnt, &q_rank_slot, &q_rank_cnt,
-                     &q_rec_off, &q_recs, &geom, &bbox, &bbox_acc};
-    for (DevBuf* b : all) b->release();
-  }
-};

@@ -14,7 +14,7 @@
 // without materialising raypos[R,400,3] (3.1 GB for an 800^2 frame).
 #include <algorithm>
 
-#include "pnr_common.h"
+#include "grid_tables.h"
 
 namespace pnr {
 
@@ -682,6 +682,24 @@ extern "C" int pnr_query_scratch_bytes(int64_t R, int32_t SR, size_t* out) {
   return PNR_OK;
 }
 
+// k_knn's instantiation.  KMAX: the smallest of 8 / 16 / 32 that holds K.  The
+// 3x3x3 kernel (layers == 2) has its own instantiation where cells index in 32
+// bits, with the large batch unless the launch is small; everything else runs
+// the generic one.
+using KnnKernel = decltype(&k_knn<8, 0, kKnnBatchSmall>);
+template <int KM>
+static KnnKernel knn_kernel_of(bool q3, bool small) {
+  return q3 ? (small ? k_knn<KM, 2, kKnnBatchSmall> : k_knn<KM, 2, kKnnBatch>) : k_knn<KM, 0, kKnnBatchSmall>;
+}
+static KnnKernel knn_kernel(int K, int layers, bool cells32, bool small) {
+  const bool q3 = layers == 2 && cells32;
+  return K <= 8 ? knn_kernel_of<8>(q3, small) : K <= 16 ? knn_kernel_of<16>(q3, small) : knn_kernel_of<32>(q3, small);
+}
+
+// k_knn's per-XCD chunk counters: the head of the caller's scan scratch, free
+// between the fill-list and valid-list scans (stream order)
+static int32_t* knn_chunk_counters(const pnr_query_bufs* b) { return reinterpret_cast<int32_t*>(b->scratch); }
+
 static int check_rays(const pnr_rays* r) {
   PNR_CHECK_ARG(r && r->campos_dev && r->camrot_dev && r->raydir_dev && r->tvals_dev,
                 "rays: null pointer");
@@ -706,9 +724,10 @@ extern "C" int pnr_query(pnr_handle* h, const pnr_rays* rays, const pnr_query_pa
   PNR_CHECK_ARG(b->scratch_bytes >= std::max<size_t>(scan_scratch_bytes(RS + 1), 64), "query: scratch too small");
   hipStream_t st = as_stream(stream);
   QRays q = to_qrays(rays);
-  // the grid's exact geometry lives on the device (h->geom); h->gp.dims bounds it
-  const QGrid* g_dev = h->geom.as<QGrid>();
-  const int* gdims = h->gp.dims;
+  // the grid's exact geometry lives on the device; h->bound_dims bounds it
+  const QGrid* g_dev = h->tab<QGrid>(GB_GEOM);
+  const int* gdims = h->bound_dims;
+  const uint32_t* occ_bits = h->tab<uint32_t>(GB_OCC_BITS);
   PNR_HIP(hipMemsetAsync(b->counts, 0, 8 * sizeof(int32_t), st));
   PNR_HIP(hipMemsetAsync(b->ray_vcnt, 0, (size_t)(R > 0 ? R : 1) * sizeof(int32_t), st));
   if (R == 0) {
@@ -719,10 +738,10 @@ extern "C" int pnr_query(pnr_handle* h, const pnr_rays* rays, const pnr_query_pa
   }
   if (R <= kMarchCoopRays)   // few rays: 16 lanes per ray (latency)
     hipLaunchKernelGGL((k_march_coop<16, 2>), dim3(grid_for(R * 16, kQBlock)), dim3(kQBlock), 0, st, q, g_dev, qp->SR,
-                       h->occ_bits.as<uint32_t>(), b->n_filled, b->slot_d);
+                       occ_bits, b->n_filled, b->slot_d);
   else
     hipLaunchKernelGGL((k_march_coop<kMarchLanes, kMarchUnroll>), dim3(grid_for(R * kMarchLanes, kQBlock, kMarchGridCap)),
-                       dim3(kQBlock), 0, st, q, g_dev, qp->SR, h->occ_bits.as<uint32_t>(), b->n_filled, b->slot_d);
+                       dim3(kQBlock), 0, st, q, g_dev, qp->SR, occ_bits, b->n_filled, b->slot_d);
   PNR_LAUNCH_CHECK();
   if ((rc = exclusive_scan(b->n_filled, R, nullptr, b->ray_off, R + 1, b->counts + 0, b->scratch,
                            b->scratch_bytes, st)))
@@ -735,28 +754,19 @@ extern "C" int pnr_query(pnr_handle* h, const pnr_rays* rays, const pnr_query_pa
   // chip holds, so more records in flight per lane
   const bool small = RS < (int64_t(4) << 20);
   // the 3x3x3 kernel indexes cells in 32 bits
-  const bool q3 = layers == 2 && (int64_t)gdims[0] * gdims[1] * gdims[2] < (int64_t(1) << 32);
+  const bool cells32 = (int64_t)gdims[0] * gdims[1] * gdims[2] < (int64_t(1) << 32);
   unsigned gk = grid_for(RS, kQBlock, kKnnGrid);
   if (gk >= 8) gk &= ~7u;   // whole XCD groups (k_knn's chunk walk)
-  // k_knn's per-XCD chunk counters: the head of the scan scratch, free between
-  // the fill-list and valid-list scans (stream order)
-  PNR_HIP(hipMemsetAsync(b->scratch, 0, 8 * sizeof(int32_t), st));
+  PNR_HIP(hipMemsetAsync(knn_chunk_counters(b), 0, 8 * sizeof(int32_t), st));
   const int vec = ((uintptr_t)b->pidx & 15) == 0;
   QIndex qi;
-  qi.words = h->q_words.as<uint2>();
-  qi.coarse = reinterpret_cast<const uint32_t*>(h->cell_bytes.as<uint8_t>() + h->coarse_off);
-  qi.rec_off = h->q_rec_off.as<int32_t>();
-  qi.recs = h->q_recs.as<float4>();
-#define PNR_KNN(KM)                                                                              \
-  hipLaunchKernelGGL((q3 ? (small ? k_knn<KM, 2, kKnnBatchSmall> : k_knn<KM, 2, kKnnBatch>)           \
-                          : k_knn<KM, 0, kKnnBatchSmall>), dim3(gk), dim3(kQBlock), 0, st, q, g_dev, qp->SR, qp->K, layers,      \
-                     qp->radius_limit2, qi, b->slot_d, b->fill_rs, b->pidx, b->vflag,             \
-                     b->ray_vcnt, b->sample_w, b->sample_p, b->counts, vec,                       \
-                     reinterpret_cast<int32_t*>(b->scratch))
-  if (qp->K <= 8) PNR_KNN(8);
-  else if (qp->K <= 16) PNR_KNN(16);
-  else PNR_KNN(32);
-#undef PNR_KNN
+  qi.words = h->tab<uint2>(GB_Q_WORDS);
+  qi.coarse = reinterpret_cast<const uint32_t*>(h->cell_bytes(h->lay.coarse_off));
+  qi.rec_off = h->tab<int32_t>(GB_Q_REC_OFF);
+  qi.recs = h->tab<float4>(GB_Q_RECS);
+  hipLaunchKernelGGL(knn_kernel(qp->K, layers, cells32, small), dim3(gk), dim3(kQBlock), 0, st, q, g_dev, qp->SR, qp->K,
+                     layers, qp->radius_limit2, qi, b->slot_d, b->fill_rs, b->pidx, b->vflag, b->ray_vcnt, b->sample_w,
+                     b->sample_p, b->counts, vec, knn_chunk_counters(b));
   PNR_LAUNCH_CHECK();
   // valid_off and, in the same pass, valid_list[valid_off[i]] = i for vflag[i] (the
   // separate compaction re-read both arrays: c5 117 us)

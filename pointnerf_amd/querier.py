@@ -16,6 +16,9 @@ so ``NeuralPoints.__init__`` (neural_points.py:330-331) can select it with
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -41,13 +44,14 @@ def ray_mid_t(near: float, far: float, D: int, R: int = 1, jitter: float = 0.0,
     return mid[0].to(device) if device is not None else mid[0]
 
 
-def hyperparameters_from_bbox(opt, min_xyz: np.ndarray, max_xyz: np.ndarray):
-    """get_hyperparameters (qpiw.py:48-81) given the exact point bbox; the
-    same numpy/torch dtype promotions as the reference."""
-    vsize_np = opt.vsize
-    vscale_np = np.array(opt.vscale, dtype=np.int32)
+def _hyperparameters(vsize, vscale, kernel_size, ranges, radius_limit_scale, depth_limit_scale, min_xyz, max_xyz):
+    """get_hyperparameters (qpiw.py:48-81) given the exact point bbox, with the
+    numpy/torch dtype promotions of the reference (vsize goes in as the caller
+    holds it: a list of Python floats promotes to float64).  ranges None or
+    min >= max: unset.  Returns (hp, pad)."""
+    vsize_np = vsize
+    vscale_np = np.array(vscale, dtype=np.int32)
     scaled_vsize_np = (vsize_np * vscale_np).astype(np.float32)
-    ranges = opt.ranges
     if ranges is not None and ranges[0] >= ranges[3]:
         ranges = None
     min_xyz = np.asarray(min_xyz, np.float32)
@@ -55,17 +59,117 @@ def hyperparameters_from_bbox(opt, min_xyz: np.ndarray, max_xyz: np.ndarray):
     if ranges is not None:
         min_xyz = np.maximum(min_xyz, np.asarray(ranges[:3], dtype=np.float32))
         max_xyz = np.minimum(max_xyz, np.asarray(ranges[3:], dtype=np.float32))
-    pad = (scaled_vsize_np * opt.kernel_size / 2).astype(np.float32)
+    pad = (scaled_vsize_np * kernel_size / 2).astype(np.float32)
     min_xyz = (min_xyz - pad).astype(np.float32)
     max_xyz = (max_xyz + pad).astype(np.float32)
     ranges_np = np.concatenate([min_xyz, max_xyz]).astype(np.float32)
     vdim_np = (max_xyz - min_xyz) / vsize_np
     scaled_vdim_np = np.ceil(vdim_np / vscale_np).astype(np.int32)
-    radius_limit_np = np.asarray(opt.radius_limit_scale * max(vsize_np[0], vsize_np[1])).astype(np.float32)
-    depth_limit_np = np.asarray(opt.depth_limit_scale * vsize_np[2]).astype(np.float32)
-    return dict(ranges=ranges_np, shift=ranges_np[:3].copy(), vsize_s=scaled_vsize_np,
-                dims=scaled_vdim_np, radius_limit=radius_limit_np, depth_limit=depth_limit_np,
-                radius_limit2=np.float32(radius_limit_np ** 2), vsize=vsize_np, vscale=vscale_np)
+    radius_limit_np = np.asarray(radius_limit_scale * max(vsize_np[0], vsize_np[1])).astype(np.float32)
+    depth_limit_np = np.asarray(depth_limit_scale * vsize_np[2]).astype(np.float32)
+    hp = dict(ranges=ranges_np, shift=ranges_np[:3].copy(), vsize_s=scaled_vsize_np,
+              dims=scaled_vdim_np, radius_limit=radius_limit_np, depth_limit=depth_limit_np,
+              radius_limit2=np.float32(radius_limit_np ** 2), vsize=vsize_np, vscale=vscale_np)
+    return hp, pad
+
+
+def hyperparameters_from_bbox(opt, min_xyz: np.ndarray, max_xyz: np.ndarray):
+    """get_hyperparameters (qpiw.py:48-81) given the exact point bbox; the
+    same numpy/torch dtype promotions as the reference."""
+    return _hyperparameters(opt.vsize, opt.vscale, opt.kernel_size, opt.ranges, opt.radius_limit_scale,
+                            opt.depth_limit_scale, min_xyz, max_xyz)[0]
+
+
+@dataclass(frozen=True)
+class GridOpts:
+    """The options a grid build reads, once: the only place their getattr
+    defaults and the max_o_policy validation live.  Hashable: the option half of
+    GridHandle's rebuild key (the point half is (data_ptr, _version, n))."""
+    vsize: tuple
+    vscale: tuple
+    kernel_size: tuple
+    query_size: tuple
+    ranges: tuple | None        # None: unset, or min >= max (qpiw.py:61-62)
+    max_o: int
+    P: int
+    slot0_drop: int
+    grid_seed: int
+    policy: str                 # max_o_policy: "reservoir" (the reference's semantics) or "grow"
+    host_bbox: bool             # grid_host_bbox: read the bbox on the host though the device could derive it
+    dev_max_cells: int          # grid_dev_max_cells: largest ranges box the device build sizes its tables for
+    radius_limit_scale: float   # these two only shape the returned hp
+    depth_limit_scale: float
+
+    @classmethod
+    def from_opt(cls, opt) -> "GridOpts":
+        policy = getattr(opt, "max_o_policy", "reservoir")
+        if policy not in ("reservoir", "grow"):
+            raise L.PnrError(f"max_o_policy {policy!r}: 'reservoir' (the reference's semantics) or 'grow'")
+        r = getattr(opt, "ranges", None)
+        return cls(vsize=tuple(float(x) for x in opt.vsize), vscale=tuple(int(x) for x in opt.vscale),
+                   kernel_size=tuple(int(x) for x in opt.kernel_size),
+                   query_size=tuple(int(x) for x in opt.query_size),
+                   ranges=None if r is None or r[0] >= r[3] else tuple(float(x) for x in r),
+                   max_o=int(opt.max_o), P=int(opt.P), slot0_drop=int(getattr(opt, "slot0_drop", 1)),
+                   grid_seed=int(getattr(opt, "grid_seed", 0)), policy=policy,
+                   host_bbox=bool(getattr(opt, "grid_host_bbox", False)),
+                   dev_max_cells=int(getattr(opt, "grid_dev_max_cells", 1 << 28)),
+                   radius_limit_scale=float(opt.radius_limit_scale), depth_limit_scale=float(opt.depth_limit_scale))
+
+    def hyperparameters(self, min_xyz, max_xyz):
+        """(hp, pad) of a bbox (hyperparameters_from_bbox; the pad is computed there and nowhere else)."""
+        return _hyperparameters(list(self.vsize), self.vscale, self.kernel_size, self.ranges, self.radius_limit_scale,
+                                self.depth_limit_scale, min_xyz, max_xyz)
+
+    def spec(self):
+        """The point-independent half of get_hyperparameters as pnr_grid_spec,
+        plus the host dict entries that do not depend on the bbox; (None, None)
+        without ranges (the bbox then decides the extent)."""
+        if self.ranges is None:
+            return None, None
+        ranges = np.asarray(self.ranges, np.float32)
+        hp_max, pad = self.hyperparameters(ranges[:3], ranges[3:])   # the bbox = ranges case: the dims' bound
+        sp = L.GridSpec()
+        sp.ranges[:] = [float(x) for x in ranges]
+        sp.pad[:] = [float(x) for x in pad]
+        sp.vsize[:] = self.vsize
+        sp.vscale[:] = self.vscale
+        sp.vsize_s[:] = [float(x) for x in hp_max["vsize_s"]]
+        sp.dims_max[:] = [int(x) for x in hp_max["dims"]]
+        sp.query_size[:] = self.query_size
+        sp.max_o, sp.P, sp.slot0_drop, sp.seed = self.max_o, self.P, self.slot0_drop, self.grid_seed
+        base = {k: v for k, v in hp_max.items() if k not in ("shift", "dims", "ranges")}
+        base.update(pad=pad, opt_ranges=ranges)
+        return sp, base
+
+    def params(self, hp, max_o: int) -> L.GridParams:
+        """pnr_grid_params of the exact geometry hp (hyperparameters of the points' bbox)."""
+        gp = L.GridParams()
+        gp.shift[:] = [float(x) for x in hp["shift"]]
+        gp.vsize[:] = [float(x) for x in hp["vsize_s"]]
+        gp.dims[:] = [int(x) for x in hp["dims"]]
+        gp.query_size[:] = self.query_size
+        gp.max_o, gp.P, gp.slot0_drop, gp.seed = int(max_o), self.P, self.slot0_drop, self.grid_seed
+        return gp
+
+    def plan(self, sp):
+        """(path, why): which build runs for these options -- "dev" (bbox and
+        geometry on the device, no host sync), "host" (the bbox read on the host)
+        or "grow" (the host build, then max_o raised to the occupied voxels).
+        sp: self.spec()[0]."""
+        if self.policy == "grow":
+            return "grow", "max_o_policy 'grow' reads the voxel count on the host anyway"
+        if sp is None:
+            return "host", "no ranges: the bbox decides the extent"
+        cells = int(np.prod(np.asarray(list(sp.dims_max), np.int64)))
+        if cells > self.dev_max_cells:
+            # the device path sizes its tables for the whole ranges box (it does not know the bbox
+            # before the build): a room-scale box at a fine voxel size (ScanNet: +-10 m, 0.016 m
+            # cells ~ 2G cells ~ 29 GB) takes the host bbox path instead
+            return "host", f"ranges box of {cells} cells over grid_dev_max_cells = {self.dev_max_cells}"
+        if self.host_bbox:
+            return "host", "grid_host_bbox"
+        return "dev", "ranges set and within the cell budget"
 
 
 class GridHP(dict):
@@ -107,42 +211,25 @@ class GridHP(dict):
         return dict.__getitem__(self, key)
 
 
-GRID_BYTES_PER_CELL = 13.5   # cell tables of one build: coor_2_occ, cell_start / cell_end, dilated bytes, bitmaps
+# Bytes of per-cell tables one build allocates, per cell of the (allocation-bound) grid, as
+# GridLayout (csrc/grid_tables.h) sizes them: GB_COOR_2_OCC, GB_CELL_START and GB_CELL_END at 4 B
+# per cell; per 32-cell word GB_CELL_BYTES' occupancy, held and word-rank regions (32 + 32 + 4 B),
+# GB_OCC_BITS (4 B), GB_Q_WORDS (8 B) and GB_Q_WCNT (4 B); GB_CELL_BYTES' coarse map at 4 B per
+# 8 x 32 (z, y) cells.  (The per-point and per-slot tables are not in it.)
+GRID_BYTES_PER_CELL = 3 * 4 + (68 + 4 + 8 + 4) / 32 + 4 / (8 * 32)   # 14.640625
 
 
 def grid_dev_max_cells(opt) -> int:
     """Largest ranges-box grid (cells) the sync-free device build sizes its tables
-    for (opt.grid_dev_max_cells, default 2^28 ~ 3.6 GB of tables); bigger boxes
+    for (opt.grid_dev_max_cells, default 2^28 ~ 3.9 GB of tables); bigger boxes
     build on the host-read bbox."""
-    return int(getattr(opt, "grid_dev_max_cells", 1 << 28))
+    return GridOpts.from_opt(opt).dev_max_cells
 
 
 def grid_spec(opt):
-    """The point-independent half of get_hyperparameters (qpiw.py:48-81) as
-    pnr_grid_spec, plus the host dict entries; None when opt.ranges is unset
-    (the bbox then decides the extent: host path)."""
-    ranges = opt.ranges
-    if ranges is None or ranges[0] >= ranges[3]:
-        return None, None
-    vsize_np = opt.vsize
-    vscale_np = np.array(opt.vscale, dtype=np.int32)
-    scaled_vsize_np = (vsize_np * vscale_np).astype(np.float32)
-    pad = (scaled_vsize_np * opt.kernel_size / 2).astype(np.float32)
-    hp_max = hyperparameters_from_bbox(opt, np.asarray(ranges[:3], np.float32), np.asarray(ranges[3:], np.float32))
-    sp = L.GridSpec()
-    sp.ranges[:] = [float(x) for x in np.asarray(ranges, np.float32)]
-    sp.pad[:] = [float(x) for x in pad]
-    sp.vsize[:] = [float(x) for x in vsize_np]
-    sp.vscale[:] = [int(x) for x in vscale_np]
-    sp.vsize_s[:] = [float(x) for x in scaled_vsize_np]
-    sp.dims_max[:] = [int(x) for x in hp_max["dims"]]
-    sp.query_size[:] = [int(x) for x in opt.query_size]
-    sp.max_o, sp.P = int(opt.max_o), int(opt.P)
-    sp.slot0_drop = int(getattr(opt, "slot0_drop", 1))
-    sp.seed = int(getattr(opt, "grid_seed", 0))
-    base = {k: v for k, v in hp_max.items() if k not in ("shift", "dims", "ranges")}
-    base.update(pad=pad, opt_ranges=np.asarray(ranges, np.float32))
-    return sp, base
+    """GridOpts.spec of opt: pnr_grid_spec plus the host dict entries; (None,
+    None) when opt.ranges is unset."""
+    return GridOpts.from_opt(opt).spec()
 
 
 class QueryBuffers:
@@ -272,6 +359,7 @@ class GridHandle:
         self.key = None
         self.hp = None
         self.gen = 0
+        self.path = self.path_why = None   # GridOpts.plan of the last build
 
     def close(self):
         """Free the grid now (explicit; refused during stream capture)."""
@@ -303,59 +391,55 @@ class GridHandle:
         return np.array(list(out)[3:], np.float32)
 
     def build(self, opt, xyz: torch.Tensor, force: bool = False):
-        """get_hyperparameters + build_occ_vox; skipped when the point tensor is
-        unchanged (same storage, same version counter)."""
+        """get_hyperparameters + build_occ_vox; skipped when the point tensor
+        (same storage, same version counter) and the grid options are unchanged."""
         xyz = xyz.reshape(-1, 3)
         L.require_gpu(xyz)
         assert xyz.dtype == torch.float32 and xyz.is_contiguous()
-        policy = getattr(opt, "max_o_policy", "reservoir")
-        if policy not in ("reservoir", "grow"):
-            raise L.PnrError(f"max_o_policy {policy!r}: 'reservoir' (the reference's semantics) or 'grow'")
-        key = (xyz.data_ptr(), xyz._version, xyz.shape[0], tuple(opt.vsize), tuple(opt.vscale),
-               tuple(opt.kernel_size), tuple(opt.query_size), tuple(opt.ranges), opt.max_o, opt.P,
-               int(getattr(opt, "slot0_drop", 1)), int(getattr(opt, "grid_seed", 0)), policy)
+        go = GridOpts.from_opt(opt)
+        key = (xyz.data_ptr(), xyz._version, xyz.shape[0], go)
         if not force and key == self.key:
             return self.hp
         release_deferred()
         self.gen += 1
-        sp, base = grid_spec(opt) if policy == "reservoir" else (None, None)
-        if sp is not None and int(np.prod(np.asarray(list(sp.dims_max), np.int64))) > grid_dev_max_cells(opt):
-            # the device path sizes its tables for the whole ranges box (it does not know the
-            # bbox before the build): a room-scale box at a fine voxel size (ScanNet: +-10 m,
-            # 0.016 m cells ~ 2G cells ~ 27 GB) takes the host bbox path instead
-            sp = None
-        if sp is not None and not getattr(opt, "grid_host_bbox", False):
-            # no host sync: bbox -> get_hyperparameters -> build, all on the device
-            L.check(L.lib().pnr_grid_build_dev(self.h, L.ptr(xyz), xyz.shape[0], L.ctypes.byref(sp),
-                                               L.stream_ptr(xyz.device)), "pnr_grid_build_dev")
-            self._xyz = xyz
-            hp = GridHP(self, base, self.gen)
-            self.key, self.hp = key, hp
-            self._max_o, self._P = int(sp.max_o), int(opt.P)
-            return hp
-        mn, mx = self.bbox(xyz)
-        hp = hyperparameters_from_bbox(opt, mn, mx)
-        gp = L.GridParams()
-        gp.shift[:] = [float(x) for x in hp["shift"]]
-        gp.vsize[:] = [float(x) for x in hp["vsize_s"]]
-        gp.dims[:] = [int(x) for x in hp["dims"]]
-        gp.query_size[:] = [int(x) for x in opt.query_size]
-        gp.max_o, gp.P = int(opt.max_o), int(opt.P)
-        gp.slot0_drop = int(getattr(opt, "slot0_drop", 1))
-        gp.seed = int(getattr(opt, "grid_seed", 0))
+        sp, base = go.spec()
+        self.path, self.path_why = go.plan(sp)
+        if self.path == "dev":
+            hp, max_o = self._build_dev(xyz, sp, base)
+        elif self.path == "host":
+            hp, max_o = self._build_host(go, xyz, go.max_o)
+        else:
+            hp, max_o = self._build_grow(go, xyz)
+        self.key, self.hp = key, hp
+        self._max_o, self._P = max_o, go.P
+        return hp
+
+    def _build_dev(self, xyz, sp, base):
+        """No host sync: bbox -> get_hyperparameters -> build, all on the device."""
+        L.check(L.lib().pnr_grid_build_dev(self.h, L.ptr(xyz), xyz.shape[0], L.ctypes.byref(sp),
+                                           L.stream_ptr(xyz.device)), "pnr_grid_build_dev")
+        self._xyz = xyz
+        return GridHP(self, base, self.gen), int(sp.max_o)
+
+    def _build_host(self, go, xyz, max_o, hp=None):
+        """The bbox read on the host (one sync), its exact geometry handed to the build."""
+        if hp is None:
+            hp = go.hyperparameters(*self.bbox(xyz))[0]
+        gp = go.params(hp, max_o)
         L.check(L.lib().pnr_grid_build(self.h, L.ptr(xyz), xyz.shape[0], L.ctypes.byref(gp),
                                        L.stream_ptr(xyz.device)), "pnr_grid_build")
-        if policy == "grow" and xyz.shape[0] > gp.max_o:
-            # max_o raised to the occupied voxels (one host read of the count, once per
-            # point-cloud version): no voxel is dropped, the reservoir only acts on P
-            nv = self._stats_raw().n_voxels
-            if nv > gp.max_o:
-                gp.max_o = int(nv)
-                L.check(L.lib().pnr_grid_build(self.h, L.ptr(xyz), xyz.shape[0], L.ctypes.byref(gp),
-                                               L.stream_ptr(xyz.device)), "pnr_grid_build")
-        self.key, self.hp = key, hp
-        self._max_o, self._P = int(gp.max_o), int(opt.P)
-        return hp
+        return hp, int(max_o)
+
+    def _build_grow(self, go, xyz):
+        """The host build, then max_o raised to the occupied voxels (one host read of
+        the count, once per point-cloud version) and the build again: no voxel is
+        dropped, the reservoir only acts on P."""
+        hp, max_o = self._build_host(go, xyz, go.max_o)
+        if xyz.shape[0] > max_o:
+            nv = int(self._stats_raw().n_voxels)
+            if nv > max_o:
+                return self._build_host(go, xyz, nv, hp)
+        return hp, max_o
 
     def _stats_raw(self):
         s = L.GridStats()
@@ -444,9 +528,7 @@ class lighting_fast_querier:  # noqa: N801  (reference class name)
 
     def get_hyperparameters(self, vsize_np, point_xyz_w_tensor, ranges=None):
         mn, mx = self.grid.bbox(point_xyz_w_tensor.reshape(-1, 3).contiguous())
-        o = self.opt
-        from types import SimpleNamespace
-        o2 = SimpleNamespace(**{**vars(o), "vsize": vsize_np, "ranges": ranges})
+        o2 = SimpleNamespace(**{**vars(self.opt), "vsize": vsize_np, "ranges": ranges})
         return hyperparameters_from_bbox(o2, mn, mx)
 
     def tvals(self, near, far, R, device):

@@ -350,3 +350,123 @@ def test_device_grid_cell_budget_takes_host_path(cuda):
     td, tb = q_dev.grid.export(), q_b.grid.export()
     for k in td:
         assert torch.equal(td[k], tb[k]), k
+
+
+def _grid_state(q, sc, opt, xyz, cuda):
+    """After building opt's grid of xyz on q: export(), one query's outputs, stats()."""
+    q.opt = opt
+    bufs, _, _, _ = q.run(xyz, torch.from_numpy(sc["raydir"]).to(cuda), torch.from_numpy(sc["campos"]).to(cuda),
+                          torch.from_numpy(sc["camrot"]).to(cuda), 2.0, 6.0)
+    out = dict(q.grid.export())
+    c = bufs.read_counts()
+    S = c["S_filled"]
+    out.update(counts=bufs.counts.clone(), pidx=bufs.pidx[: S * opt.K].clone(), sample_w=bufs.sample_w[: S * 3].clone(),
+               sample_p=bufs.sample_p[: S * 3].clone(), valid_list=bufs.valid_list[: c["S_valid"]].clone())
+    return out, q.grid.stats()
+
+
+@pytest.mark.parametrize("host_bbox", [False, True])
+def test_one_handle_reused_across_sizes_equals_fresh_handles(cuda, host_bbox):
+    """A handle that shrinks and regrows -- voxel overflow at 20000 points, then
+    3 points, then the full tables -- leaves after each build the tables, the
+    statistics and the query of a fresh handle given only that build, bit for
+    bit: every table offset and every reused buffer comes from the build at
+    hand, none from an earlier, larger one."""
+    from types import SimpleNamespace
+    sc = scene(20000, H=24, W=24, theta=70.0)
+    reused = _engine(sc, cuda)
+    for n, max_o, P in [(20000, 1500, 1), (3, 8, 2), (20000, 830000, 9)]:
+        opt = SimpleNamespace(**{**vars(sc["opt"]), "max_o": max_o, "P": P, "grid_host_bbox": host_bbox})
+        xyz = torch.from_numpy(sc["xyz"][:n].copy()).to(cuda)
+        got, got_st = _grid_state(reused, sc, opt, xyz, cuda)
+        want, want_st = _grid_state(_engine(sc, cuda), sc, opt, xyz, cuda)
+        assert got_st == want_st, (n, got_st, want_st)
+        assert got_st["device_geometry"] == (not host_bbox)
+        for k in want:
+            assert torch.equal(got[k], want[k]), (n, k)
+        if max_o == 1500:
+            assert got_st["n_voxels"] > max_o and got_st["n_points_dropped"] > 0   # both reservoirs ran
+        if n == 20000 and max_o == 830000:
+            assert int(got["counts"][1]) > 1000, "the last build must serve a real query"
+
+
+def test_grid_refusals_with_a_real_handle(cuda):
+    """Every refused build or query returns PNR_EINVAL with its message and
+    leaves the grid that was built: the same export() and the same query."""
+    import ctypes
+    from pointnerf_amd import _lib as L
+    from pointnerf_amd.querier import (GridHandle, QueryBuffers, camera_tables, grid_spec, hyperparameters_from_bbox,
+                                       make_rays, query_params)
+    sc = scene(20000, H=24, W=24, theta=70.0)
+    opt = sc["opt"]
+    xyz = torch.from_numpy(sc["xyz"]).to(cuda)
+    rd = torch.from_numpy(sc["raydir"]).to(cuda)
+    cp, cr = camera_tables(torch.from_numpy(sc["campos"]).to(cuda), torch.from_numpy(sc["camrot"]).to(cuda))
+    from pointnerf_amd.querier import ray_mid_t
+    tv = ray_mid_t(2.0, 6.0, opt.z_depth_dim)[0].to(cuda).contiguous()
+    rays = make_rays(cp, cr, rd, tv, False)
+    R = rd.shape[0]
+    lib, stream = L.lib(), L.stream_ptr(cuda)
+    g = GridHandle(cuda)
+
+    def refused(rc, message):
+        assert rc == L.PNR_EINVAL, rc
+        assert lib.pnr_last_error().decode() == message
+
+    def query(bufs, qp):
+        return lib.pnr_query(g.h, ctypes.byref(rays), ctypes.byref(qp), ctypes.byref(bufs.c), stream)
+
+    hp = hyperparameters_from_bbox(opt, sc["xyz"].min(0), sc["xyz"].max(0))
+    bufs = QueryBuffers(R, opt.SR, opt.K, cuda)
+    refused(query(bufs, query_params(opt, hp)), "query: grid not built (call pnr_grid_build first)")
+
+    g.build(opt, xyz)
+    before = g.export()
+    assert query(bufs, query_params(opt, hp)) == L.PNR_OK
+    c = bufs.read_counts()
+    filled = c["S_filled"] * opt.K                 # the query writes pidx of the filled samples only
+    pidx_before = bufs.pidx[:filled].clone()
+    assert c["S_valid"] > 1000
+
+    def params(**over):
+        gp = L.GridParams()
+        gp.shift[:] = [float(x) for x in hp["shift"]]
+        gp.vsize[:] = [float(x) for x in hp["vsize_s"]]
+        gp.dims[:] = [int(x) for x in hp["dims"]]
+        gp.query_size[:] = [int(x) for x in opt.query_size]
+        gp.max_o, gp.P, gp.slot0_drop, gp.seed = opt.max_o, opt.P, 1, 0
+        for k, v in over.items():
+            if isinstance(v, tuple):
+                getattr(gp, k)[v[0]] = v[1]
+            else:
+                setattr(gp, k, v)
+        return gp
+
+    def build(gp, n=xyz.shape[0]):
+        return lib.pnr_grid_build(g.h, L.ptr(xyz), n, ctypes.byref(gp), stream)
+
+    refused(build(params(dims=(1, 0))), "grid_build: empty grid dims")
+    refused(build(params(max_o=0)), "grid_build: max_o and P must be > 0")
+    refused(build(params(P=0)), "grid_build: max_o and P must be > 0")
+    refused(build(params(vsize=(2, 0.0))), "grid_build: vsize <= 0")
+    refused(build(params(), n=0), "grid_build: point count 0 out of range")
+    sp, _ = grid_spec(opt)
+    sp.ranges[4] = sp.ranges[1]
+    refused(lib.pnr_grid_build_dev(g.h, L.ptr(xyz), xyz.shape[0], ctypes.byref(sp), stream),
+            "grid_build_dev: needs ranges (min < max)")
+    qp = query_params(opt, hp)
+    qp.K = 33
+    refused(query(bufs, qp), f"query: SR={opt.SR} K=33 unsupported")
+    need = L.c_size_t(0)
+    L.check(lib.pnr_query_scratch_bytes(R, opt.SR, ctypes.byref(need)), "pnr_query_scratch_bytes")
+    short = QueryBuffers(R, opt.SR, opt.K, cuda)
+    short.c.scratch_bytes = need.value - 1
+    refused(query(short, query_params(opt, hp)), "query: scratch too small")
+
+    after = g.export()
+    for k in before:
+        assert torch.equal(before[k], after[k]), k
+    bufs.pidx.fill_(-7)
+    assert query(bufs, query_params(opt, hp)) == L.PNR_OK
+    assert bufs.read_counts() == c and torch.equal(bufs.pidx[:filled], pidx_before)
+    g.close()
