@@ -281,5 +281,8 @@ __device__ __forceinline__ float xork_sum_nc(float v) {
 int launch_color_h2(const pnr_samples& s, const pnr_mlp& w, const void* const pack[4], const float scale[3],
                     int32_t* range_flag, const float* hid, const int32_t* vmask, float* out_feat, hipStream_t st,
                     const float* rw2c_pp, const pnr_agg_saved* train = nullptr);
+// k_pairs_h2's hid planes -> the fp32 rows [n_max][256] k_color reads, in place
+// (pnr_aggregate_fwd_h2 without colour packs: the fp32 colour branch).
+int launch_hid_rows_h2(float* hid, int64_t n_max, hipStream_t st);
 
 }  // namespace pnr

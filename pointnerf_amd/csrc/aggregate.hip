@@ -938,6 +938,8 @@ static int aggregate_forward(const FwdCall& c, const pnr_points* pts, const pnr_
                          c.saved);
     return rc || !guarded ? rc : launch_t<true>(f, st, kStageColor);
   }
+  // the inference k_pairs_h2 leaves hid as f16-split planes (k_color_h2's input): rows for k_color
+  if (h2 && !c.train() && (rc = launch_hid_rows_h2(a.hid, s->n_max, st))) return rc;
   return fp32(a, kStageColor);
 }
 

@@ -1498,6 +1498,51 @@ int launch_color_h2(const pnr_samples& s, const pnr_mlp& w, const void* const pa
   return PNR_OK;
 }
 
+namespace {
+
+// k_pairs_h2's hid planes (kHidTile layout) -> fp32 rows [64][256] of the same
+// 64 KB, in place, one workgroup per 64-sample tile: x = xh + 2^-11 xl, the value
+// k_color_h2 multiplies.  Thread t: sample t & 63, row groups 8 (t >> 6) .. + 7;
+// every piece of the tile is in registers before the first row is written.
+// Rows k_pairs_h2 never wrote (no neighbour, past n) stay junk, as in the planes.
+// A cold branch, kept plain: all cdiv(n_max, 64) tiles are converted whatever
+// *n_dev says, and the barrier that ends the loop body is not needed (the next
+// tile is other memory).
+__global__ void __launch_bounds__(256) k_hid_rows_h2(float* hid, int64_t tiles) {
+  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+  const int s = threadIdx.x & 63, g0 = 8 * (threadIdx.x >> 6);
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    char* base = reinterpret_cast<char*>(hid) + tile * kHidTile;
+    uint4 hi[8], lo[8];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      hi[g] = *reinterpret_cast<const uint4*>(base + ((g0 + g) * kXT + s) * 16);
+      lo[g] = *reinterpret_cast<const uint4*>(base + kHidPlane + ((g0 + g) * kXT + s) * 16);
+    }
+    __syncthreads();
+    float* row = hid + (tile * kXT + s) * kHid;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      const h8 a = __builtin_bit_cast(h8, hi[g]), b = __builtin_bit_cast(h8, lo[g]);
+      float x[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) x[i] = fmaf((float)b[i], 1.f / 2048.f, (float)a[i]);
+      float4* dst = reinterpret_cast<float4*>(row + 8 * (g0 + g));
+      dst[0] = make_float4(x[0], x[1], x[2], x[3]);
+      dst[1] = make_float4(x[4], x[5], x[6], x[7]);
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+int launch_hid_rows_h2(float* hid, int64_t n_max, hipStream_t st) {
+  const int64_t tiles = cdiv(n_max, kXT);
+  hipLaunchKernelGGL(k_hid_rows_h2, dim3(grid_for(tiles, 1, 256 * 8)), dim3(256), 0, st, hid, tiles);
+  PNR_LAUNCH_CHECK();
+  return PNR_OK;
+}
 
 template <bool H>
 int launch_pairs_split(const pnr_points& pts, const pnr_samples& s, const pnr_mlp& w, const SplitW& wx,
