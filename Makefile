@@ -25,6 +25,8 @@ build/query.o build/grid.o build/voxelize.o: HIPFLAGS += -ffp-contract=off
 build/rays.o build/seed.o: HIPFLAGS += -ffp-contract=off
 # The depth-map fusion's reprojections and thresholds likewise.
 build/fuse.o: HIPFLAGS += -ffp-contract=off
+# The perspective query's binning, centres and distances likewise.
+build/pquery.o: HIPFLAGS += -ffp-contract=off
 # The bf16 pair kernel's gather math (weights, distances, PE) without FMA
 # contraction: its render and general instantiations then round every fp32 op
 # the same way, so their features agree bit for bit (test_gpu_bf16.py).

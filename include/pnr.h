@@ -58,6 +58,10 @@
  *   pnr_depth_fuse,
  *   pnr_depth_points     <- the geometric filter of gen_points: posed depth maps to a cloud
  *                           models/mvs/filter_utils.py:157-297 (filter_by_masks_gpu)
+ *   pnr_pquery,
+ *   pnr_pquery_compact   <- the perspective-frustum querier (--wcoord_query 0): get_occ_vox, near_vox_full,
+ *                           insert_vox_points, query_neigh_along_ray_layered
+ *                           models/neural_points/query_point_indices.py:265-413, 495-600
  */
 #ifndef PNR_H_
 #define PNR_H_
@@ -71,7 +75,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 28
+#define PNR_ABI_VERSION 29
 
 enum {
   PNR_OK = 0,
@@ -1216,6 +1220,85 @@ int pnr_depth_points(const int32_t* src, int64_t M, const float* depth_avg, cons
                      const float* conf, const float* cams, int32_t F, int32_t H, int32_t W,
                      const pnr_fuse_params* params_host, float* xyz, float* conf_out, int64_t* src_pixel,
                      int32_t* count_out, int64_t out_cap, void* stream);
+
+/* ------------------------------------------------- perspective query (ABI 29) */
+/* The reference's perspective-frustum querier (--wcoord_query 0):
+ * the cloud in perspective coordinates (x/z, y/z, z) is binned into a frustum
+ * grid of dims cells (x = image column / vscale[0], y = image row / vscale[1],
+ * z = depth), cell (x * dims[1] + y) * dims[2] + z, of scaled_vsize each from
+ * shift.  All fp32, one rounding per operation, in the reference's order.
+ *
+ *  - A point holds the voxel floor((p - shift) / scaled_vsize) (dropped outside
+ *    the grid); a held voxel c marks [c - q/2, c + (q+1)/2) per axis (q =
+ *    query_size, clipped) as occupied.
+ *  - A point is listed in the voxel of the quotient truncated toward zero (so
+ *    a quotient in (-1, 0) lists it in voxel 0 of that axis), in ascending id,
+ *    when some point holds that voxel.  A voxel listing more than P points
+ *    keeps the P of smallest res_hash32(grid_seed + salt, id), ascending id (the
+ *    world grid's rule).
+ *  - Ray r has pixel (px, py) = pixel_idx[2r], pixel_idx[2r+1] and column
+ *    (px / vscale[0], py / vscale[1]).  ray_mask = the column's largest
+ *    occupied depth id > 0.  Its SR slots are the column's first SR occupied ids
+ *    ascending, then -1.
+ *  - Sample (r, slot) with depth id fz: centre cx = shift[0] + fx scaled_vsize[0]
+ *    + (px % vscale[0] + 0.5) ray_vsize[0], cy likewise, cz = shift[2] + (fz + 0.5)
+ *    scaled_vsize[2] (the 0.5 terms in double, as the reference's literals
+ *    promote them); written to sample_loc also for fz = -1.  Neighbours: layers
+ *    0 .. (kernel_size[0]+1)/2 - 1, x and y in -layer..layer, z in -zl..zl with zl =
+ *    min((kernel_size[2]+1)/2 - 1, layer), clipped, order x, y, z; a voxel is
+ *    skipped when max(|x|,|y|) != layer and (zl == layer ? |z| != zl : true).  A
+ *    listed point (X, Y, Z): x_v = X - cx (NN < 2) or X Z - cx cz, y_v likewise,
+ *    xy2 = x_v^2 + y_v^2, z2 = (Z - cz)^2; accepted when (radius_limit2 == 0 || xy2
+ *    <= radius_limit2) && (depth_limit2 == 0 || z2 <= depth_limit2).  The first K
+ *    accepted fill the slots in visit order; then a point replaces the first
+ *    farthest (by xy2 + z2) only when strictly closer.  No early break.
+ *
+ * Refused on the host (PNR_EINVAL): NN < 1 (the random query), K outside
+ * 1..32, sizes outside 1..15, and a kernel_size wider than query_size --
+ * (kernel_size[0]+1)/2 - 1 must not exceed (query_size[i]+1)/2 - 1 for i = 0, 1
+ * and min of it and (kernel_size[2]+1)/2 - 1 not (query_size[2]+1)/2 - 1 --
+ * because then the reference's result for a ray depends on the other rays of
+ * its batch.  Here it never does.
+ * Pixels outside [0, w) x [0, h) are misses, points with a non-finite
+ * coordinate or quotient are dropped; both are counted.
+ *
+ * pnr_pquery writes, on the caller's stream and without a host sync:
+ *   ray_mask [R] int8; counts[0] = R' = the hit rays (device int32 block of 4);
+ *   stats (device); and, for the hit rays in ray order (row i = the i-th hit
+ *   ray), sample_pidx [R,SR,K] (-1 where empty), sample_loc [R,SR,3], slot_z
+ *   [R,SR] (the depth ids) -- rows R' .. R are not written.
+ * pnr_pquery_compact copies the first R' rows of sample_pidx / sample_loc into
+ * tensors of exactly that size.  scratch from pnr_pquery_scratch_bytes. */
+typedef struct {
+  float shift[3];         /* ranges[0..2] */
+  float scaled_vsize[3];  /* vsize * vscale */
+  float ray_vsize[3];     /* scaled_vsize / vscale */
+  int32_t dims[3];        /* ceil((w, h, z_depth_dim) / vscale) */
+  int32_t vscale[3];
+  int32_t w, h;           /* the frame pixel_idx indexes */
+  int32_t SR, K, P, NN;
+  int32_t kernel_size[3];
+  int32_t query_size[3];
+  float radius_limit2;    /* 0: no test */
+  float depth_limit2;     /* 0: no test */
+  uint64_t grid_seed;
+} pnr_pquery_params;
+typedef struct {
+  int32_t n_points_in_grid;      /* points that hold a voxel */
+  int32_t n_voxels_held;
+  int32_t max_held_per_column;   /* the reference's int8 slot ranks alias past min(127, max_o) */
+  int32_t max_points_per_voxel;  /* listed in one held voxel, before the P cap */
+  int32_t n_voxels_over_p;
+  int32_t n_bad_pixels;
+  int32_t n_bad_points;
+  int32_t reserved;
+} pnr_pquery_stats;
+int pnr_pquery_scratch_bytes(int64_t N, int64_t R, int32_t SR, const int32_t* dims, size_t* out);
+int pnr_pquery(const pnr_pquery_params* params_host, const float* xyz_pers, int64_t N, const int32_t* pixel_idx,
+               int64_t R, int32_t* sample_pidx, float* sample_loc, int32_t* slot_z, int8_t* ray_mask, int32_t* counts,
+               pnr_pquery_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
+int pnr_pquery_compact(const int32_t* pidx_rows, const float* loc_rows, int64_t R, int32_t SR, int32_t K, int64_t R_hit,
+                       int32_t* sample_pidx, float* sample_loc, void* stream);
 
 /* ------------------------------------------------------------- optimizer */
 /* One Adam step (torch.optim.Adam, amsgrad = False: the optimizer of the

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PNR_LIB", os.path.join(_HERE, "libpnr.so"))
 c_int, c_int8, c_int32, c_int64 = ctypes.c_int, ctypes.c_int8, ctypes.c_int32, ctypes.c_int64
 c_float, c_size_t, c_void_p = ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 PNR_OK, PNR_EINVAL, PNR_EOVERFLOW, PNR_EHIP, PNR_ENOMEM = 0, 1, 2, 3, 4
-ABI_VERSION = 28
+ABI_VERSION = 29
 SEED_CAM_TILE = 64   # PNR_SEED_CAM_TILE (include/pnr.h)
 FEAT_H_PITCH = 136   # PNR_FEAT_H_PITCH: uint16 per bf16 feature row (pnr_aggregate_fwd_bf16_hf)
 HEAD_BWD_BLOCKS = 512   # PNR_HEAD_BWD_BLOCKS (include/pnr.h)
@@ -159,6 +159,18 @@ class AggGrads(ctypes.Structure):
 class FuseParams(ctypes.Structure):
     _fields_ = [("pix_thresh", c_float), ("rel_thresh", c_float), ("conf_thresh", c_float),
                 ("geo_cnsst_num", c_int32), ("reassign_conf", c_int32), ("ranges", c_float * 6)]
+
+
+class PQueryParams(ctypes.Structure):
+    _fields_ = [("shift", c_float * 3), ("scaled_vsize", c_float * 3), ("ray_vsize", c_float * 3),
+                ("dims", c_int32 * 3), ("vscale", c_int32 * 3), ("w", c_int32), ("h", c_int32), ("SR", c_int32),
+                ("K", c_int32), ("P", c_int32), ("NN", c_int32), ("kernel_size", c_int32 * 3),
+                ("query_size", c_int32 * 3), ("radius_limit2", c_float), ("depth_limit2", c_float),
+                ("grid_seed", ctypes.c_uint64)]
+
+
+PQUERY_STATS = ("n_points_in_grid", "n_voxels_held", "max_held_per_column", "max_points_per_voxel",
+                "n_voxels_over_p", "n_bad_pixels", "n_bad_points")   # pnr_pquery_stats: int32 each, 8 words
 
 
 class MlpBwdH2(ctypes.Structure):
@@ -338,6 +350,11 @@ SIGNATURES = {
                                c_void_p]),
     "pnr_depth_points": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                  P(FuseParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "pnr_pquery_scratch_bytes": (c_int, [c_int64, c_int64, c_int32, P(c_int32), P(c_size_t)]),
+    "pnr_pquery": (c_int, [P(PQueryParams), c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnr_pquery_compact": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p, c_void_p,
+                                   c_void_p]),
     "pnr_scan_scratch_bytes": (c_int, [c_int64, P(c_size_t)]),
     "pnr_exclusive_scan_i32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_size_t, c_void_p]),

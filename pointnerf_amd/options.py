@@ -50,6 +50,13 @@ FLAGSETS = {
                   near_plane=0.0, far_plane=3.5, default_conf=0.1),
 }
 
+# dev_scripts/ete/dtu_dgt_d012_img0123_conf_color_dir_agg2.sh and dev_scripts/dtu_test_inf/*.sh: the feed-forward
+# DTU case, rendered by the perspective-frustum querier (they leave --wcoord_query at its default 0;
+# querier_p.py).  vsize / ranges / max_o are world-grid flags the perspective query does not read.
+DTU = dict(vscale=[2, 2, 1], kernel_size=[3, 3, 3], query_size=[3, 3, 3], SR=40, K=8, P=20, NN=2,
+           radius_limit_scale=0.0, depth_limit_scale=0.0, near_plane=2.0, far_plane=4.725,
+           z_depth_dim=400, wcoord_query=0, shpnt_jitter="passfunc")
+
 
 def lego_opt(**over):
     o = dict(LEGO)
@@ -57,6 +64,14 @@ def lego_opt(**over):
     if o["query_size"][0] == 0:
         o["query_size"] = list(o["kernel_size"])
     return SimpleNamespace(**o)
+
+
+def dtu_opt(**over):
+    """The DTU scripts' flag set (DTU): the perspective query, wcoord_query 0.
+    Kept out of FLAGSETS, whose entries are world-grid scenes."""
+    o = dict(DTU)
+    o.update(over)
+    return lego_opt(**o)
 
 
 def flagset_opt(name: str, **over):

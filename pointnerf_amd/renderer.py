@@ -23,12 +23,15 @@ import torch.nn as nn
 from . import _lib as L
 from .aggregator import PointAggregator
 from .querier import COUNT_R_VALID, camera_tables, counts_dict, lighting_fast_querier, release_deferred
+from .querier_p import lighting_fast_querier as lighting_fast_querier_p
 from .render_eval import EAGER, QUEUED, RayBatch, RenderGraph, _RenderCall, _RenderState, bg_channels  # noqa: F401
 from .render_train import TRAIN_BYTES_PER_SAMPLE, _TrainAux, _TrainCall, march_aux  # noqa: F401
 
 
 class NeuralPoints(nn.Module):
-    """Point table of neural_points.NeuralPoints (world-coordinate querier)."""
+    """Point table of neural_points.NeuralPoints; opt.wcoord_query picks the
+    querier as neural_points.py:330 does: > 0 the world grid (querier.py), 0 the
+    perspective frustum (querier_p.py)."""
 
     def __init__(self, opt, device, xyz=None, embedding=None, color=None, dirs=None, conf=None,
                  Rw2c=None, emb_dtype=torch.float32):
@@ -50,7 +53,8 @@ class NeuralPoints(nn.Module):
         self.Rw2c = torch.eye(3, device=self.device)
         if xyz is not None:
             self.set_points(xyz, embedding, color, dirs, conf, Rw2c)
-        self.querier = lighting_fast_querier(self.device, opt)
+        self.perspective = getattr(opt, "wcoord_query", 1) <= 0
+        self.querier = (lighting_fast_querier_p if self.perspective else lighting_fast_querier)(self.device, opt)
 
     def set_points(self, xyz, embedding, color=None, dirs=None, conf=None, Rw2c=None):
         """set_points (neural_points.py:480-546) with point_*_mode '1'; xyz is
@@ -127,8 +131,15 @@ class NeuralPoints(nn.Module):
         camrotc2w, campos = inputs["camrotc2w"], inputs["campos"]
         near, far = inputs["near"], inputs["far"]
         pers = self.w2pers(self.xyz, camrotc2w, campos)
+        pixel_idx = inputs.get("pixel_idx")
+        if self.perspective:
+            for name in ("pixel_idx", "h", "w", "intrinsic"):
+                if inputs.get(name) is None:
+                    raise L.PnrError(f"NeuralPoints.forward with wcoord_query 0 (the perspective query) needs "
+                                     f"inputs[{name!r}]")
+            pixel_idx = pixel_idx.to(torch.int32)
         (sample_pidx, sample_loc, sample_loc_w, sample_ray_dirs, ray_mask, vsize, ranges) = \
-            self.querier.query_points(inputs.get("pixel_idx"), pers, self.xyz[None, ...], None,
+            self.querier.query_points(pixel_idx, pers, self.xyz[None, ...], None,
                                       inputs.get("h"), inputs.get("w"), inputs.get("intrinsic"),
                                       torch.min(near).item(), torch.max(far).item(), inputs["raydir"],
                                       campos, camrotc2w)
@@ -247,6 +258,11 @@ class NeuralPointsRayMarching(nn.Module):
                 getattr(opt, "which_tonemap_func", "off") != "off":
             raise L.PnrError("libpnr implements radiance render, alpha blend and tone map 'off'")
 
+    def _world_only(self, who: str):
+        if self.neural_points.perspective:
+            raise L.PnrError(f"{who}: the fused frame is world-query only; call the module (forward) with "
+                             "wcoord_query 0")
+
     def _sync_rw2c(self):
         """The aggregator renders with NeuralPoints.Rw2c (neural_points.py:289;
         applied to view dirs, distances and point dirs at
@@ -304,6 +320,7 @@ class NeuralPointsRayMarching(nn.Module):
         chunk); if an activation left the f16 range, the call is rendered again
         on the fp32x3 path (bf16 split: same accuracy, fp32 range) and h2 stays
         off for these weights until they change (``h2_fallbacks`` counts it)."""
+        self._world_only("render_rays")
         self._sync_rw2c()
         if self._pending and (sync or self._sv_per_ray is None):
             # a synchronous call reads (and may clear) the shared range flag and the
@@ -329,6 +346,7 @@ class NeuralPointsRayMarching(nn.Module):
 
     def _render_rays(self, mode, precision, batch, state, **options):
         """One render call (render_eval._RenderCall and its modes) -> (outputs, its _PendingCall or None)."""
+        self._world_only("render_rays / RenderGraph")
         return _RenderCall(self, mode, precision, batch, state, **options).run()
 
     def render_camera(self, campos, camrotc2w, intrinsic, H, W, near, far, bg_color, dir_norm=False, **kw):
@@ -469,6 +487,7 @@ class NeuralPointsRayMarching(nn.Module):
         render_train._TrainCall).  Returns ray_color
         [R,C] (requires grad w.r.t. points_embeding / color / dir / conf and the
         aggregator parameters), opacity [R,SR], is_bg [R], ray_mask [R]."""
+        self._world_only("render_rays_train")
         return _TrainCall(self, campos, camrot, raydir, near, far, bg_color).run()
 
     def wants_aux(self) -> bool:
@@ -486,6 +505,7 @@ class NeuralPointsRayMarching(nn.Module):
         evaluation render (render_rays keeps no per-pair state): the batch's
         query again, then pnr_query_compact + pnr_march_aux on the rendered
         opacity.  conf_coefficient carries no graph here (no_grad render)."""
+        self._world_only("eval_aux")
         np_ = self.neural_points
         dev = raydir.device
         cp, cr = camera_tables(campos, camrot, None)
@@ -503,6 +523,7 @@ class NeuralPointsRayMarching(nn.Module):
         the rendered opacity [R,SR] -- no compaction, no [R'',SR,K,*] tensors, no
         host read.  Shapes [1,R,1] / [1,R,3] / [1,R,32]; None for an absent
         point table; rows of rays without a neighbour are zeros."""
+        self._world_only("probe_maps")
         np_ = self.neural_points
         raydir = raydir.reshape(-1, 3).float().contiguous()
         dev = raydir.device
@@ -587,6 +608,66 @@ class NeuralPointsRayMarching(nn.Module):
         v = torch.clamp(val, zero_epsilon, 1 - zero_epsilon)
         return torch.mean(torch.log(v) + torch.log(1 - v))
 
+    def _forward_perspective(self, campos, raydir, gt_image, bg_color, camrotc2w, pixel_idx, near, far, focal, h, w,
+                             intrinsic):
+        """forward with wcoord_query 0: the reference's forward as its seams
+        (neural_points_volumetric_model.py:288-341) -- NeuralPoints.forward's
+        14-tuple (pnr_pquery), PointAggregator.forward (the fused aggregate,
+        differentiable), ray_dist, ray_march, fill_invalid.  ray_mask is the
+        querier's (the column's far id > 0): a hit ray without any neighbour
+        keeps ray_mask 1 and composites to the background."""
+        from .ray_march import alpha_blend, radiance_render, ray_march
+        if getattr(self.opt, "prob", 0) == 1:
+            raise L.PnrError("opt.prob == 1 (the point-growing probe) is world-query only")
+        self._sync_rw2c()
+        (s_color, s_rw2c, s_dir, s_conf, s_emb, s_pers, s_xyz, s_mask, s_loc, s_loc_w, s_dirs, ray_mask, vsize,
+         grid_vox_sz) = self.neural_points({"pixel_idx": pixel_idx, "camrotc2w": camrotc2w, "campos": campos,
+                                            "near": near, "far": far, "focal": focal, "h": h, "w": w,
+                                            "intrinsic": intrinsic, "gt_image": gt_image, "raydir": raydir})
+        feats, ray_valid, weight, conf = self.aggregator(s_color, s_rw2c, s_dir, s_conf, s_emb, s_pers, s_xyz, s_mask,
+                                                         s_loc, s_loc_w, s_dirs, vsize, grid_vox_sz)
+        vz = float(vsize[2])   # the querier's (far - near) / z_depth_dim
+        rd = torch.cummax(s_loc[..., 2], dim=-1)[0]
+        rd = torch.cat([rd[..., 1:] - rd[..., :-1], torch.full(rd.shape[:2] + (1,), vz, device=rd.device)], dim=-1)
+        m = rd < 1e-8
+        if self.opt.raydist_mode_unit > 0:
+            m = torch.logical_or(m, rd > 2 * vz)
+        m = m.to(torch.float32)
+        rd = (rd * (1.0 - m) + m * vz) * ray_valid.float()
+        if rd.shape[1] == 0:   # no ray hit: nothing to march, fill_invalid writes every row
+            f32 = dict(dtype=torch.float32, device=rd.device)
+            color, opacity = torch.zeros((1, 0, feats.shape[-1] - 1), **f32), torch.zeros((1, 0, rd.shape[2]), **f32)
+            blend_weight, bg_T = torch.zeros((1, 0, rd.shape[2], 1), **f32), torch.zeros((1, 0, 1), **f32)
+        else:
+            color, _, opacity, _, blend_weight, bg_T, _ = ray_march(rd, ray_valid, feats, radiance_render, alpha_blend,
+                                                                    bg_color)
+        # fill_invalid (:354-389)
+        B, R = ray_mask.shape
+        dev = color.device
+        hit = ray_mask[0] > 0
+        C = color.shape[-1]
+        bg = torch.zeros(C, device=dev) if bg_color is None else bg_color.to(dev).float().reshape(-1)
+        full_color = (torch.ones((B, R, C), dtype=color.dtype, device=dev) * bg[None, None, :])
+        full_color[:, hit] = color
+        full_bg = torch.ones((B, R, 1), dtype=bg_T.dtype, device=dev)
+        full_bg[:, hit] = bg_T
+        full_op = torch.zeros((B, R, opacity.shape[2]), dtype=opacity.dtype, device=dev)
+        full_op[:, hit] = opacity
+        shading = torch.ones((B, R, 3), dtype=torch.float32, device=dev)
+        shading[:, hit] = torch.logical_not(torch.any(ray_valid, dim=-1, keepdim=True)).repeat(1, 1, 3).float()
+        out = dict(coarse_raycolor=full_color, coarse_point_opacity=full_op, coarse_is_background=full_bg,
+                   ray_mask=ray_mask, coarse_mask=1 - full_bg, queried_shading=shading)
+        if weight is not None:   # :335-338
+            out["weight"] = weight.detach()
+            out["blend_weight"] = blend_weight.detach()
+            out["conf_coefficient"] = conf
+        if self.neural_render_2d is not None:
+            img_h = int(h.item()) if torch.is_tensor(h) else int(h)
+            img_w = int(w.item()) if torch.is_tensor(w) else int(w)
+            out["final_coarse_raycolor"] = self.neural_render_2d(
+                out["coarse_raycolor"].reshape(1, img_h, img_w, -1)).reshape(1, -1, 3)
+        return out
+
     def forward(self, campos, raydir, gt_image=None, bg_color=None, camrotc2w=None, pixel_idx=None,
                 near=None, far=None, focal=None, h=None, w=None, intrinsic=None, **kargs):
         """neural_points_volumetric_model.py:272-352 (+ fill_invalid :354-389);
@@ -598,6 +679,9 @@ class NeuralPointsRayMarching(nn.Module):
         far_v = float(torch.max(far).item()) if torch.is_tensor(far) else float(far)
         if "bg_ray" in kargs:
             bg_color = None
+        if self.neural_points.perspective:
+            return self._forward_perspective(campos, raydir, gt_image, bg_color, camrotc2w, pixel_idx, near, far,
+                                             focal, h, w, intrinsic)
         # training loop (model(...) then loss.backward(), as run/train_ft.py does):
         # differentiable path; evaluation / no_grad: the fused forward
         train = torch.is_grad_enabled() and self.training and (
