@@ -62,6 +62,10 @@
  *   pnr_pquery_compact   <- the perspective-frustum querier (--wcoord_query 0): get_occ_vox, near_vox_full,
  *                           insert_vox_points, query_neigh_along_ray_layered
  *                           models/neural_points/query_point_indices.py:265-413, 495-600
+ *   pnr_pquery_build,
+ *   pnr_pquery_bufs,
+ *   pnr_composite_fwd_p  <- the same querier plus pers2w (:104-116) and the module's ray_dist / ray_march /
+ *                           fill_invalid, as one frame on the device (no gathered pair tensor)
  */
 #ifndef PNR_H_
 #define PNR_H_
@@ -75,7 +79,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 29
+#define PNR_ABI_VERSION 30
 
 enum {
   PNR_OK = 0,
@@ -1299,6 +1303,55 @@ int pnr_pquery(const pnr_pquery_params* params_host, const float* xyz_pers, int6
                pnr_pquery_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
 int pnr_pquery_compact(const int32_t* pidx_rows, const float* loc_rows, int64_t R, int32_t SR, int32_t K, int64_t R_hit,
                        int32_t* sample_pidx, float* sample_loc, void* stream);
+
+/* ------------------------------------- fused perspective frame (ABI 30) */
+/* The perspective query feeding the fused frame: the same query
+ * as pnr_pquery, split into the part that depends on the camera and the cloud
+ * and the part that depends on the rays, the latter writing the world query's
+ * pnr_query_bufs so that the aggregate (pnr_samples) and the composite walk them
+ * unchanged.  No [R,SR,.] rows, no host read.
+ *
+ * pnr_pquery_build: bin, scatter, dilate, records and the statistics (stats as
+ *   pnr_pquery writes them, n_bad_pixels 0) into `build`, at least
+ *   pnr_pquery_scratch_bytes(N, 0, SR, dims) bytes.  One build serves every
+ *   pnr_pquery_bufs call with the same params, N and points.
+ * pnr_pquery_bufs: for the R pixels, in the caller's order,
+ *   ray_hit [R] int8   = pnr_pquery's ray_mask;
+ *   n_filled[r]        = min(SR, occupied depth ids of the column) of a hit ray,
+ *                        0 of a miss; ray_off its exclusive scan; counts[0] =
+ *                        S_filled;
+ *   and for filled sample i = ray_off[r] + s (s < n_filled[r]):
+ *   fill_rs[i] = r SR + s; slot_d[i] = the depth id fz (>= 0: a slot without an
+ *   id is not filled); pidx[i,K], sample_p[i] = pnr_pquery's row (r, s) of
+ *   sample_pidx / sample_loc bit for bit (the same device code walks both);
+ *   sample_w[i] and sample_dir[i,3] = pers2w of the centre
+ *   (query_point_indices.py:104-116) in fp32, one rounding per operation:
+ *   xyz_c = (cx cz, cy cz, cz), shift_i = (xyz_c[0] camrot[i][0] + xyz_c[1]
+ *   camrot[i][1]) + xyz_c[2] camrot[i][2], dir = shift / (|shift| + 1e-7), w =
+ *   shift + campos; vflag[i] = some pidx[i,k] >= 0.
+ *   valid_off, valid_list, ray_vcnt, ray_row and counts[1..4] as pnr_query
+ *   defines them (R_hit = hit rays, R_valid = rays with a valid sample, n_pairs
+ *   = ids >= 0); counts[5..7] = 0.  b->scratch as for pnr_query
+ *   (pnr_query_scratch_bytes(R, SR)).  campos [3], camrot [3,3] camrotc2w:
+ *   device.  `build`, build_bytes, N: what pnr_pquery_build was given.
+ *   The aggregate takes dirs = sample_dir with dir_map NULL and dir_div 1.
+ * Refused (PNR_EINVAL) besides pnr_pquery's rules: K > 8 (the aggregate's
+ *   limit), dims[2] > 65535 (slot_d), null pointers.
+ *
+ * pnr_composite_fwd_p: pnr_composite_fwd on such buffers (fp32 feature rows).
+ *   A ray is a hit when ray_hit[r] != 0 -- also without a valid sample: it then
+ *   marches empty slots to opacity 0, colour bg, is_bg 1, ray_mask 1 -- and an
+ *   unfilled slot lies at depth z_unfilled, the centre depth of fz = -1:
+ *   (float)((double)shift[2] - 0.5 (double)scaled_vsize[2]).  A missed ray gives
+ *   bg (or 0), opacity 0, is_bg 1, ray_mask 0 whatever its rows hold. */
+int pnr_pquery_build(const pnr_pquery_params* params_host, const float* xyz_pers, int64_t N, pnr_pquery_stats* stats,
+                     void* build, size_t build_bytes, void* stream);
+int pnr_pquery_bufs(const pnr_pquery_params* params_host, int64_t N, const int32_t* pixel_idx, int64_t R,
+                    const float* campos, const float* camrot, pnr_query_bufs* b, int8_t* ray_hit, float* sample_dir,
+                    const void* build, size_t build_bytes, void* stream);
+int pnr_composite_fwd_p(const pnr_query_params* q, const pnr_query_bufs* b, const pnr_composite_params* c, int64_t R,
+                        const int8_t* ray_hit, float z_unfilled, const float* feat, float* ray_color, float* opacity,
+                        float* is_bg, int8_t* ray_mask, void* stream);
 
 /* ------------------------------------------------------------- optimizer */
 /* One Adam step (torch.optim.Adam, amsgrad = False: the optimizer of the

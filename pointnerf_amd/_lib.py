@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PNR_LIB", os.path.join(_HERE, "libpnr.so"))
 c_int, c_int8, c_int32, c_int64 = ctypes.c_int, ctypes.c_int8, ctypes.c_int32, ctypes.c_int64
 c_float, c_size_t, c_void_p = ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 PNR_OK, PNR_EINVAL, PNR_EOVERFLOW, PNR_EHIP, PNR_ENOMEM = 0, 1, 2, 3, 4
-ABI_VERSION = 29
+ABI_VERSION = 30
 SEED_CAM_TILE = 64   # PNR_SEED_CAM_TILE (include/pnr.h)
 FEAT_H_PITCH = 136   # PNR_FEAT_H_PITCH: uint16 per bf16 feature row (pnr_aggregate_fwd_bf16_hf)
 HEAD_BWD_BLOCKS = 512   # PNR_HEAD_BWD_BLOCKS (include/pnr.h)
@@ -355,6 +355,11 @@ SIGNATURES = {
                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnr_pquery_compact": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p, c_void_p,
                                    c_void_p]),
+    "pnr_pquery_build": (c_int, [P(PQueryParams), c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnr_pquery_bufs": (c_int, [P(PQueryParams), c_int64, c_void_p, c_int64, c_void_p, c_void_p, P(QueryBufs),
+                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnr_composite_fwd_p": (c_int, [P(QueryParams), P(QueryBufs), P(CompositeParams), c_int64, c_void_p, c_float,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnr_scan_scratch_bytes": (c_int, [c_int64, P(c_size_t)]),
     "pnr_exclusive_scan_i32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_size_t, c_void_p]),

@@ -97,6 +97,9 @@ struct CompArgs {
   float* opacity;
   float* is_bg;
   int8_t* ray_mask;
+  // the perspective mode (pnr_composite_fwd_p)
+  const int8_t* ray_hit;   // [R] the querier's ray_mask
+  float z_unfilled;        // depth of every unfilled slot
 };
 
 // Camera-space depth of the world origin: the z of every unfilled slot
@@ -115,7 +118,11 @@ __device__ float origin_depth(const CompArgs& a, int64_t cam) {
 
 // HF: features from pnr_aggregate_fwd_bf16_hf's bf16 rows -- lane l holds
 // channels 2l and 2l + 1 (one 4-B load per row), alpha the row's fp32 head.
-template <bool HF>
+// PERSP: the buffers of the perspective query (pnr_pquery_bufs).  A ray is a hit
+// when the querier says so (ray_hit), also without any valid sample -- it then
+// marches SR empty slots to opacity 0 and bg * 1 -- and the unfilled slots lie at
+// the querier's fz = -1 centre depth instead of the world origin's.
+template <bool HF, bool PERSP = false>
 __global__ void __launch_bounds__(kCBlock) k_composite(CompArgs a) {
   constexpr int NRW = kCRows;   // feature rows in flight (bf16 rows too: 12 / 16 measured slower at c5)
   const int lane = threadIdx.x & 63;
@@ -123,10 +130,18 @@ __global__ void __launch_bounds__(kCBlock) k_composite(CompArgs a) {
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const int SR = a.SR, C = a.C, CF = C + 1;
   // depth of the world origin: the z of every unfilled slot (sample_loc_w = 0)
-  const float zo0 = origin_depth(a, 0);
+  float zo0;
+  if constexpr (PERSP)
+    zo0 = a.z_unfilled;
+  else
+    zo0 = origin_depth(a, 0);
   const float vz = a.vsize_z, two_vz = 2.f * a.vsize_z;
   for (int64_t r = wave0; r < a.R; r += nwaves) {
-    const bool mask = a.ray_vcnt[r] > 0;
+    bool mask;
+    if constexpr (PERSP)
+      mask = a.ray_hit[r] != 0;
+    else
+      mask = a.ray_vcnt[r] > 0;
     if (!mask) {  // fill_invalid: background ray
       for (int c = lane; c < C; c += 64) a.ray_color[r * C + c] = a.bg ? a.bg[c] : 0.f;
       for (int s = lane; s < SR; s += 64) a.opacity[r * SR + s] = 0.f;
@@ -137,7 +152,9 @@ __global__ void __launch_bounds__(kCBlock) k_composite(CompArgs a) {
       continue;
     }
     const int n = a.n_filled[r], off = a.ray_off[r];
-    const float zo = a.ray_cam ? origin_depth(a, a.ray_cam[r]) : zo0;
+    float zo = zo0;
+    if constexpr (!PERSP)
+      if (a.ray_cam) zo = origin_depth(a, a.ray_cam[r]);
     float z[2], sig[2];
     int vrow[2];
 #pragma unroll
@@ -661,20 +678,11 @@ __global__ void __launch_bounds__(kCBlock) k_march_aux(AuxArgs a) {
 
 using namespace pnr;
 
-static int composite_fwd(const pnr_rays* rays, const pnr_query_params* q, const pnr_query_bufs* b,
-                         const pnr_composite_params* c, const float* feat, const uint16_t* feat_h, float* ray_color,
-                         float* opacity, float* is_bg, int8_t* ray_mask, void* stream) {
-  PNR_CHECK_ARG(rays && q && b && c && ray_color && opacity && is_bg && ray_mask,
-                "composite: null pointer");
-  PNR_CHECK_ARG(rays->campos_dev && rays->camrot_dev, "composite: camera required");
-  PNR_CHECK_ARG(q->SR >= 1 && q->SR <= 128, "composite: SR=%d unsupported (1..128)", q->SR);
-  PNR_CHECK_ARG(c->C >= 1 && c->C <= 128, "composite: C=%d unsupported (1..128)", c->C);
-  if (rays->R == 0) return PNR_OK;
-  CompArgs a;
-  a.campos = rays->campos_dev;
-  a.camrot = rays->camrot_dev;
-  a.ray_cam = rays->ray_cam;
-  a.R = rays->R;
+// What both modes read of the query buffers and the composite parameters.
+static CompArgs comp_args(const pnr_query_params* q, const pnr_query_bufs* b, const pnr_composite_params* c,
+                          const float* feat, const uint16_t* feat_h, float* ray_color, float* opacity, float* is_bg,
+                          int8_t* ray_mask) {
+  CompArgs a = {};
   a.SR = q->SR;
   a.n_filled = b->n_filled;
   a.ray_off = b->ray_off;
@@ -693,6 +701,23 @@ static int composite_fwd(const pnr_rays* rays, const pnr_query_params* q, const 
   a.opacity = opacity;
   a.is_bg = is_bg;
   a.ray_mask = ray_mask;
+  return a;
+}
+
+static int composite_fwd(const pnr_rays* rays, const pnr_query_params* q, const pnr_query_bufs* b,
+                         const pnr_composite_params* c, const float* feat, const uint16_t* feat_h, float* ray_color,
+                         float* opacity, float* is_bg, int8_t* ray_mask, void* stream) {
+  PNR_CHECK_ARG(rays && q && b && c && ray_color && opacity && is_bg && ray_mask,
+                "composite: null pointer");
+  PNR_CHECK_ARG(rays->campos_dev && rays->camrot_dev, "composite: camera required");
+  PNR_CHECK_ARG(q->SR >= 1 && q->SR <= 128, "composite: SR=%d unsupported (1..128)", q->SR);
+  PNR_CHECK_ARG(c->C >= 1 && c->C <= 128, "composite: C=%d unsupported (1..128)", c->C);
+  if (rays->R == 0) return PNR_OK;
+  CompArgs a = comp_args(q, b, c, feat, feat_h, ray_color, opacity, is_bg, ray_mask);
+  a.campos = rays->campos_dev;
+  a.camrot = rays->camrot_dev;
+  a.ray_cam = rays->ray_cam;
+  a.R = rays->R;
   const unsigned grid = grid_for(rays->R * 64, kCBlock, 256 * 16);
   if (feat_h)
     hipLaunchKernelGGL(k_composite<true>, dim3(grid), dim3(kCBlock), 0, as_stream(stream), a);
@@ -716,6 +741,27 @@ extern "C" int pnr_composite_fwd_hf(const pnr_rays* rays, const pnr_query_params
   PNR_CHECK_ARG(feat_h && c && (c->C % 2) == 0, "composite_hf: feat_h required, C even");
   PNR_CHECK_ARG(((uintptr_t)feat_h & 15) == 0, "composite_hf: feat_h must be 16-B aligned");
   return composite_fwd(rays, q, b, c, nullptr, feat_h, ray_color, opacity, is_bg, ray_mask, stream);
+}
+
+extern "C" int pnr_composite_fwd_p(const pnr_query_params* q, const pnr_query_bufs* b, const pnr_composite_params* c,
+                                   int64_t R, const int8_t* ray_hit, float z_unfilled, const float* feat,
+                                   float* ray_color, float* opacity, float* is_bg, int8_t* ray_mask, void* stream) {
+  PNR_CHECK_ARG(q && b && c && ray_color && opacity && is_bg && ray_mask, "composite_p: null pointer");
+  PNR_CHECK_ARG(R >= 0, "composite_p: R=%lld", (long long)R);
+  PNR_CHECK_ARG(q->SR >= 1 && q->SR <= 128, "composite_p: SR=%d unsupported (1..128)", q->SR);
+  PNR_CHECK_ARG(c->C >= 1 && c->C <= 128, "composite_p: C=%d unsupported (1..128)", c->C);
+  PNR_CHECK_ARG(fabsf(z_unfilled) < __builtin_inff(), "composite_p: z_unfilled is not finite");
+  if (R == 0) return PNR_OK;
+  PNR_CHECK_ARG(ray_hit && feat && b->n_filled && b->ray_off && b->vflag && b->valid_off && b->sample_p,
+                "composite_p: null buffer");
+  CompArgs a = comp_args(q, b, c, feat, nullptr, ray_color, opacity, is_bg, ray_mask);
+  a.R = R;
+  a.ray_hit = ray_hit;
+  a.z_unfilled = z_unfilled;
+  hipLaunchKernelGGL((k_composite<false, true>), dim3(grid_for(R * 64, kCBlock, 256 * 16)), dim3(kCBlock), 0,
+                     as_stream(stream), a);
+  PNR_LAUNCH_CHECK();
+  return PNR_OK;
 }
 
 extern "C" int pnr_ray_march_fwd(const float* ray_dist, const uint8_t* ray_valid, const float* feat,

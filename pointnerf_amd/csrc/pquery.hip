@@ -17,6 +17,16 @@
 //   k_pq_knn      one thread per (hit ray, slot): the slot-th occupied id, the
 //                 centre, the layered walk over the neighbouring columns' runs
 //
+// The kernels up to k_pq_colstats depend on the camera and the cloud only
+// (pq_build); the rest is per ray.  pnr_pquery_bufs is a second
+// per-ray part on the same build, writing the world query's pnr_query_bufs
+// instead of [R,SR,.] rows:
+//   k_pq_columns  one thread per ray: ray_hit and n_filled = min(SR, occupied ids)
+//   scan          n_filled -> ray_off, S_filled
+//   k_pq_fill     one thread per (ray, slot < n_filled): pq_sample (k_pq_knn's
+//                 walk), fill_rs, slot_d, pidx, sample_p, pers2w, vflag, ray_vcnt
+//   scan          vflag -> valid_off + valid_list; ray_vcnt -> ray_row
+//
 // A ray's result depends on the cloud and its own pixel only (no pixel_map
 // "first thread of the column" protocol), and no table is sized by the cell
 // count: the bitmaps take 2 bits per cell, everything else is per point, per
@@ -328,17 +338,17 @@ __device__ __forceinline__ int nth_bit(uint32_t v, int n) {
   return __ffs(v) - 1;
 }
 
+// One sample: the slot-th occupied depth id of pixel (px, py)'s column, its
+// centre and (fz >= 0) the layered walk; the accepted ids are left in `ids`.
+struct PqSample {
+  int fz;             // depth id, -1: the column has no slot-th occupied id
+  float cx, cy, cz;   // the centre
+  int kid;            // neighbours kept (<= K)
+};
+
 template <int KMAX>
-__global__ void __launch_bounds__(kPqKnnBlock) k_pq_knn(PqKnnArgs a) {
-  __shared__ int32_t ids_s[KMAX * kPqKnnBlock];
-  __shared__ float dst_s[KMAX * kPqKnnBlock];
+__device__ __forceinline__ PqSample pq_sample(const PqKnnArgs& a, int px, int py, int slot, PqIds<KMAX>& ids) {
   const PqGeom& g = a.g;
-  const int64_t t = (int64_t)blockIdx.x * kPqKnnBlock + threadIdx.x;
-  const int64_t r = t / a.SR;
-  if (r >= a.R || !a.hit[r]) return;
-  const int slot = (int)(t - r * a.SR);
-  const int64_t row = (int64_t)a.ray_off[r] * a.SR + slot;
-  const int px = a.pixel_idx[r * 2], py = a.pixel_idx[r * 2 + 1];   // inside the frame: the ray is a hit
   const int fx = px / g.vscale[0], fy = py / g.vscale[1];
   const int col = fx * g.dims[1] + fy;
   // the slot-th occupied depth id of the column, or -1
@@ -362,11 +372,7 @@ __global__ void __launch_bounds__(kPqKnnBlock) k_pq_knn(PqKnnArgs a) {
   const float cy = (float)((double)__fadd_rn(g.shift[1], __fmul_rn((float)fy, g.svs[1])) +
                            ((double)(py % g.vscale[1]) + 0.5) * (double)g.rvs[1]);
   const float cz = (float)((double)g.shift[2] + ((double)fz + 0.5) * (double)g.svs[2]);
-  reinterpret_cast<Row3*>(a.loc)[row] = Row3{cx, cy, cz};
-  a.slot_z[row] = fz;
-  int32_t* out = a.pidx + row * a.K;
   int kid = 0;
-  PqIds<KMAX> ids{ids_s + threadIdx.x, dst_s + threadIdx.x};
   if (fz >= 0) {
     int far_ind = 0;
     float far2 = 0.f;
@@ -420,7 +426,116 @@ __global__ void __launch_bounds__(kPqKnnBlock) k_pq_knn(PqKnnArgs a) {
         }
     }
   }
-  for (int i = 0; i < a.K; ++i) out[i] = i < kid ? ids.get(i) : -1;
+  return PqSample{fz, cx, cy, cz, kid};
+}
+
+template <int KMAX>
+__global__ void __launch_bounds__(kPqKnnBlock) k_pq_knn(PqKnnArgs a) {
+  __shared__ int32_t ids_s[KMAX * kPqKnnBlock];
+  __shared__ float dst_s[KMAX * kPqKnnBlock];
+  const int64_t t = (int64_t)blockIdx.x * kPqKnnBlock + threadIdx.x;
+  const int64_t r = t / a.SR;
+  if (r >= a.R || !a.hit[r]) return;
+  const int slot = (int)(t - r * a.SR);
+  const int64_t row = (int64_t)a.ray_off[r] * a.SR + slot;
+  PqIds<KMAX> ids{ids_s + threadIdx.x, dst_s + threadIdx.x};
+  // inside the frame: the ray is a hit
+  const PqSample s = pq_sample<KMAX>(a, a.pixel_idx[r * 2], a.pixel_idx[r * 2 + 1], slot, ids);
+  reinterpret_cast<Row3*>(a.loc)[row] = Row3{s.cx, s.cy, s.cz};
+  a.slot_z[row] = s.fz;
+  int32_t* out = a.pidx + row * a.K;
+  for (int i = 0; i < a.K; ++i) out[i] = i < s.kid ? ids.get(i) : -1;
+}
+
+// ------------------------------------------------- query buffers (pnr_pquery_bufs)
+// One thread per ray: ray_hit = the querier's ray_mask, n_filled = the slots
+// k_pq_knn would give a depth id (the column's occupied ids, at most SR).
+__global__ void __launch_bounds__(kPqBlock) k_pq_columns(PqGeom g, int SR, const int32_t* __restrict__ pixel_idx,
+                                                         int64_t R, const uint32_t* __restrict__ occ, int8_t* ray_hit,
+                                                         int32_t* n_filled, int32_t* counts) {
+  const int64_t r = (int64_t)blockIdx.x * kPqBlock + threadIdx.x;
+  bool hit = false;
+  if (r < R) {
+    const int px = pixel_idx[r * 2], py = pixel_idx[r * 2 + 1];
+    int far_id = -1, n = 0;
+    if (pixel_ok(px, py, g)) {
+      const uint32_t* ow = occ + (int64_t)((px / g.vscale[0]) * g.dims[1] + py / g.vscale[1]) * g.wz;
+      for (int k = 0; k < g.wz; ++k) {
+        const uint32_t v = ow[k];
+        n += __popc(v);
+        if (v) far_id = k * 32 + 31 - __clz(v);
+      }
+    }
+    hit = far_id > 0;   // near_vox_full: a column that holds depth id 0 only is a miss
+    ray_hit[r] = (int8_t)hit;
+    n_filled[r] = hit ? min(n, SR) : 0;
+  }
+  wave_count(counts + 2, hit);   // R_hit
+}
+
+struct PqFillArgs {
+  PqKnnArgs k;   // pidx / loc / slot_z / hit unused
+  const float* campos;   // [3]
+  const float* camrot;   // [3,3] camrotc2w
+  const int32_t* n_filled;
+  int32_t* fill_rs;
+  uint16_t* slot_d;
+  int32_t* pidx;        // [S_filled, K]
+  float* sample_p;      // [S_filled, 3]
+  float* sample_w;
+  float* sample_dir;
+  int32_t* vflag;
+  int32_t* ray_vcnt;
+  int32_t* counts;
+  int vec_pidx;         // pidx rows are 16-byte aligned (K % 4 == 0, aligned base)
+};
+
+// One thread per (ray, slot): a slot below n_filled has a depth id, so every
+// thread that passes the test walks (pq_sample: k_pq_knn's own code) and writes
+// filled sample ray_off[r] + slot.  pers2w (query_point_indices.py:104-116) in
+// its fp32 order: xyz_c = (cx cz, cy cz, cz), shift_i = sum_j xyz_c[j] camrot[i][j],
+// dir = shift / (|shift| + 1e-7), w = shift + campos.
+__global__ void __launch_bounds__(kPqKnnBlock) k_pq_fill(PqFillArgs f) {
+  __shared__ int32_t ids_s[8 * kPqKnnBlock];
+  __shared__ float dst_s[8 * kPqKnnBlock];
+  const PqKnnArgs& a = f.k;
+  const int64_t t = (int64_t)blockIdx.x * kPqKnnBlock + threadIdx.x;
+  const int64_t r = t / a.SR;
+  const int slot = (int)(t - r * a.SR);
+  int pairs = 0;
+  if (r < a.R && slot < f.n_filled[r]) {
+    const int64_t i = (int64_t)a.ray_off[r] + slot;
+    PqIds<8> ids{ids_s + threadIdx.x, dst_s + threadIdx.x};
+    const PqSample s = pq_sample<8>(a, a.pixel_idx[r * 2], a.pixel_idx[r * 2 + 1], slot, ids);
+    f.fill_rs[i] = (int32_t)(r * a.SR + slot);
+    f.slot_d[i] = (uint16_t)s.fz;
+    if (f.vec_pidx) {
+      int4* o4 = reinterpret_cast<int4*>(f.pidx + i * a.K);
+      for (int k = 0; k < a.K; k += 4)
+        o4[k >> 2] = make_int4(k < s.kid ? ids.get(k) : -1, k + 1 < s.kid ? ids.get(k + 1) : -1,
+                               k + 2 < s.kid ? ids.get(k + 2) : -1, k + 3 < s.kid ? ids.get(k + 3) : -1);
+    } else {
+      for (int k = 0; k < a.K; ++k) f.pidx[i * a.K + k] = k < s.kid ? ids.get(k) : -1;
+    }
+    reinterpret_cast<Row3*>(f.sample_p)[i] = Row3{s.cx, s.cy, s.cz};
+    const float xc[3] = {__fmul_rn(s.cx, s.cz), __fmul_rn(s.cy, s.cz), s.cz};
+    float sh[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+      sh[m] = __fadd_rn(__fadd_rn(__fmul_rn(xc[0], f.camrot[m * 3]), __fmul_rn(xc[1], f.camrot[m * 3 + 1])),
+                        __fmul_rn(xc[2], f.camrot[m * 3 + 2]));
+    const float n2 = __fadd_rn(__fadd_rn(__fmul_rn(sh[0], sh[0]), __fmul_rn(sh[1], sh[1])), __fmul_rn(sh[2], sh[2]));
+    const float den = __fadd_rn(__fsqrt_rn(n2), 1e-7f);
+    reinterpret_cast<Row3*>(f.sample_dir)[i] =
+        Row3{__fdiv_rn(sh[0], den), __fdiv_rn(sh[1], den), __fdiv_rn(sh[2], den)};
+    reinterpret_cast<Row3*>(f.sample_w)[i] =
+        Row3{__fadd_rn(sh[0], f.campos[0]), __fadd_rn(sh[1], f.campos[1]), __fadd_rn(sh[2], f.campos[2])};
+    f.vflag[i] = s.kid > 0;
+    if (s.kid > 0) atomicAdd(f.ray_vcnt + r, 1);
+    pairs = s.kid;
+  }
+  pairs = wave_sum_i32(pairs);
+  if ((threadIdx.x & 63) == 0 && pairs) atomicAdd(f.counts + 4, pairs);
 }
 
 // --------------------------------------------------------------- compact
@@ -483,6 +598,52 @@ inline int check_pq_sizes(const char* who, int64_t N, int64_t R, int32_t SR, int
   return PNR_OK;
 }
 
+// The per-camera part: bin, scan, scatter, dilate, column statistics, records.
+// Its tables (held, occ, col_cnt, col_off, rec, rec_z) sit in front of the
+// per-ray parts of the layout, so their places do not depend on R.
+inline int pq_build(const pnr_pquery_params& q, const PqGeom& g, const float* xyz_pers, int64_t N, const PqScratch& s,
+                    void* scratch, pnr_pquery_stats* stats, hipStream_t st) {
+  PNR_HIP(hipMemsetAsync(scratch, 0, s.zero_bytes, st));
+  PNR_HIP(hipMemsetAsync(stats, 0, sizeof(pnr_pquery_stats), st));
+  if (N > 0) {
+    hipLaunchKernelGGL(k_pq_bin, dim3((unsigned)cdiv(N, kPqBlock)), dim3(kPqBlock), 0, st, xyz_pers, N, g, s.held,
+                       s.col_cnt, s.pcol, s.pz, stats);
+    PNR_LAUNCH_CHECK();
+  }
+  if (int rc = exclusive_scan(s.col_cnt, g.columns, nullptr, s.col_off, (int64_t)g.columns + 1, nullptr, s.scan,
+                              s.scan_bytes, st))
+    return rc;
+  if (N > 0) {
+    hipLaunchKernelGGL(k_pq_scatter, dim3((unsigned)cdiv(N, kPqBlock)), dim3(kPqBlock), 0, st, N, s.pcol, s.pz,
+                       s.col_off, s.col_cur, s.keys);
+    PNR_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_pq_dilate, dim3((unsigned)cdiv((int64_t)g.columns * g.wz, kPqBlock)), dim3(kPqBlock), 0, st, g,
+                     q.query_size[0], q.query_size[1], q.query_size[2], s.held, s.occ);
+  PNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_pq_colstats, dim3((unsigned)cdiv(g.columns, kPqBlock)), dim3(kPqBlock), 0, st, g, s.held, stats);
+  PNR_LAUNCH_CHECK();
+  if (N > 0) {
+    hipLaunchKernelGGL(k_pq_records, dim3((unsigned)cdiv(N, kPqBlock)), dim3(kPqBlock), 0, st, N, g, q.P,
+                       (uint64_t)q.grid_seed, xyz_pers, s.pcol, s.pz, s.held, s.col_off, s.keys, s.rec, s.rec_z,
+                       stats);
+    PNR_LAUNCH_CHECK();
+  }
+  return PNR_OK;
+}
+
+// What the walk reads of a build, and the call's rays.
+inline PqKnnArgs pq_knn_args(const pnr_pquery_params& q, const PqGeom& g, const PqScratch& s, const int32_t* pixel_idx,
+                             int64_t R) {
+  PqKnnArgs a = {};
+  a.g = g, a.SR = q.SR, a.K = q.K, a.NN = q.NN;
+  a.layers = (q.kernel_size[0] + 1) / 2, a.zl_max = (q.kernel_size[2] + 1) / 2 - 1;
+  a.r2 = q.radius_limit2, a.d2 = q.depth_limit2;
+  a.pixel_idx = pixel_idx, a.R = R, a.held = s.held, a.occ = s.occ;
+  a.col_off = s.col_off, a.col_cnt = s.col_cnt, a.rec = s.rec, a.rec_z = s.rec_z;
+  return a;
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -514,32 +675,7 @@ extern "C" int pnr_pquery(const pnr_pquery_params* params_host, const float* xyz
   const PqScratch s = pq_layout(scratch, N, R, g.columns, g.wz);
   PNR_CHECK_ARG(scratch_bytes >= s.total, "pquery: scratch too small (%zu < %zu)", scratch_bytes, s.total);
   hipStream_t st = as_stream(stream);
-  PNR_HIP(hipMemsetAsync(scratch, 0, s.zero_bytes, st));
-  PNR_HIP(hipMemsetAsync(stats, 0, sizeof(pnr_pquery_stats), st));
-  if (N > 0) {
-    hipLaunchKernelGGL(k_pq_bin, dim3((unsigned)cdiv(N, kPqBlock)), dim3(kPqBlock), 0, st, xyz_pers, N, g, s.held,
-                       s.col_cnt, s.pcol, s.pz, stats);
-    PNR_LAUNCH_CHECK();
-  }
-  if (int rc = exclusive_scan(s.col_cnt, g.columns, nullptr, s.col_off, (int64_t)g.columns + 1, nullptr, s.scan,
-                              s.scan_bytes, st))
-    return rc;
-  if (N > 0) {
-    hipLaunchKernelGGL(k_pq_scatter, dim3((unsigned)cdiv(N, kPqBlock)), dim3(kPqBlock), 0, st, N, s.pcol, s.pz,
-                       s.col_off, s.col_cur, s.keys);
-    PNR_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_pq_dilate, dim3((unsigned)cdiv((int64_t)g.columns * g.wz, kPqBlock)), dim3(kPqBlock), 0, st, g,
-                     q.query_size[0], q.query_size[1], q.query_size[2], s.held, s.occ);
-  PNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_pq_colstats, dim3((unsigned)cdiv(g.columns, kPqBlock)), dim3(kPqBlock), 0, st, g, s.held, stats);
-  PNR_LAUNCH_CHECK();
-  if (N > 0) {
-    hipLaunchKernelGGL(k_pq_records, dim3((unsigned)cdiv(N, kPqBlock)), dim3(kPqBlock), 0, st, N, g, q.P,
-                       (uint64_t)q.grid_seed, xyz_pers, s.pcol, s.pz, s.held, s.col_off, s.keys, s.rec, s.rec_z,
-                       stats);
-    PNR_LAUNCH_CHECK();
-  }
+  if (int rc = pq_build(q, g, xyz_pers, N, s, scratch, stats, st)) return rc;
   if (R > 0) {
     hipLaunchKernelGGL(k_pq_select, dim3((unsigned)cdiv(R, kPqBlock)), dim3(kPqBlock), 0, st, g, pixel_idx, R, s.occ,
                        s.hit, ray_mask, stats);
@@ -547,12 +683,8 @@ extern "C" int pnr_pquery(const pnr_pquery_params* params_host, const float* xyz
   }
   if (int rc = exclusive_scan(s.hit, R, nullptr, s.ray_off, R + 1, counts, s.scan, s.scan_bytes, st)) return rc;
   if (R > 0) {
-    PqKnnArgs a = {};
-    a.g = g, a.SR = q.SR, a.K = q.K, a.NN = q.NN;
-    a.layers = (q.kernel_size[0] + 1) / 2, a.zl_max = (q.kernel_size[2] + 1) / 2 - 1;
-    a.r2 = q.radius_limit2, a.d2 = q.depth_limit2;
-    a.pixel_idx = pixel_idx, a.R = R, a.hit = s.hit, a.ray_off = s.ray_off, a.held = s.held, a.occ = s.occ;
-    a.col_off = s.col_off, a.col_cnt = s.col_cnt, a.rec = s.rec, a.rec_z = s.rec_z;
+    PqKnnArgs a = pq_knn_args(q, g, s, pixel_idx, R);
+    a.hit = s.hit, a.ray_off = s.ray_off;
     a.pidx = sample_pidx, a.loc = sample_loc, a.slot_z = slot_z;
     const dim3 grid((unsigned)cdiv(R * q.SR, kPqKnnBlock)), block(kPqKnnBlock);
     if (q.K <= 8)
@@ -564,6 +696,70 @@ extern "C" int pnr_pquery(const pnr_pquery_params* params_host, const float* xyz
     PNR_LAUNCH_CHECK();
   }
   return PNR_OK;
+}
+
+// The build alone, into scratch of pnr_pquery_scratch_bytes(N, 0, SR, dims): what
+// every pnr_pquery_bufs call of one camera and cloud reads.
+extern "C" int pnr_pquery_build(const pnr_pquery_params* params_host, const float* xyz_pers, int64_t N,
+                                pnr_pquery_stats* stats, void* scratch, size_t scratch_bytes, void* stream) {
+  PqGeom g;
+  if (int rc = check_pq("pquery_build", params_host, &g)) return rc;
+  const pnr_pquery_params& q = *params_host;
+  if (int rc = check_pq_sizes("pquery_build", N, 0, q.SR, q.K)) return rc;
+  PNR_CHECK_ARG(stats && scratch, "pquery_build: null pointer");
+  PNR_CHECK_ARG(N == 0 || xyz_pers, "pquery_build: null points");
+  const PqScratch s = pq_layout(scratch, N, 0, g.columns, g.wz);
+  PNR_CHECK_ARG(scratch_bytes >= s.total, "pquery_build: scratch too small (%zu < %zu)", scratch_bytes, s.total);
+  return pq_build(q, g, xyz_pers, N, s, scratch, stats, as_stream(stream));
+}
+
+extern "C" int pnr_pquery_bufs(const pnr_pquery_params* params_host, int64_t N, const int32_t* pixel_idx, int64_t R,
+                               const float* campos, const float* camrot, pnr_query_bufs* b, int8_t* ray_hit,
+                               float* sample_dir, const void* build, size_t build_bytes, void* stream) {
+  PqGeom g;
+  if (int rc = check_pq("pquery_bufs", params_host, &g)) return rc;
+  const pnr_pquery_params& q = *params_host;
+  if (int rc = check_pq_sizes("pquery_bufs", N, R, q.SR, q.K)) return rc;
+  PNR_CHECK_ARG(q.K <= 8, "pquery_bufs: K=%d (1 .. 8, the aggregate's limit)", q.K);
+  PNR_CHECK_ARG(q.dims[2] <= 65535, "pquery_bufs: dims[2]=%d depth ids do not fit slot_d (<= 65535)", q.dims[2]);
+  PNR_CHECK_ARG(b && build && campos && camrot, "pquery_bufs: null pointer");
+  PNR_CHECK_ARG(b->n_filled && b->slot_d && b->ray_off && b->fill_rs && b->pidx && b->valid_off && b->valid_list &&
+                    b->vflag && b->ray_vcnt && b->ray_row && b->sample_w && b->sample_p && b->counts && b->scratch,
+                "pquery_bufs: null buffer");
+  PNR_CHECK_ARG(R == 0 || (pixel_idx && ray_hit && sample_dir), "pquery_bufs: null ray buffer");
+  const PqScratch s = pq_layout(const_cast<void*>(build), N, 0, g.columns, g.wz);
+  PNR_CHECK_ARG(build_bytes >= s.total, "pquery_bufs: build scratch too small (%zu < %zu)", build_bytes, s.total);
+  const int64_t RS = R * q.SR;
+  PNR_CHECK_ARG(b->scratch_bytes >= scan_scratch_bytes(RS + 1), "pquery_bufs: scan scratch too small");
+  hipStream_t st = as_stream(stream);
+  PNR_HIP(hipMemsetAsync(b->counts, 0, 8 * sizeof(int32_t), st));
+  PNR_HIP(hipMemsetAsync(b->ray_vcnt, 0, (size_t)(R > 0 ? R : 1) * sizeof(int32_t), st));
+  if (R == 0) {
+    PNR_HIP(hipMemsetAsync(b->ray_off, 0, sizeof(int32_t), st));
+    PNR_HIP(hipMemsetAsync(b->ray_row, 0, sizeof(int32_t), st));
+    PNR_HIP(hipMemsetAsync(b->valid_off, 0, sizeof(int32_t), st));
+    return PNR_OK;
+  }
+  hipLaunchKernelGGL(k_pq_columns, dim3((unsigned)cdiv(R, kPqBlock)), dim3(kPqBlock), 0, st, g, q.SR, pixel_idx, R,
+                     s.occ, ray_hit, b->n_filled, b->counts);
+  PNR_LAUNCH_CHECK();
+  if (int rc = exclusive_scan(b->n_filled, R, nullptr, b->ray_off, R + 1, b->counts + 0, b->scratch, b->scratch_bytes,
+                              st))
+    return rc;
+  PqFillArgs f = {};
+  f.k = pq_knn_args(q, g, s, pixel_idx, R);
+  f.k.ray_off = b->ray_off;
+  f.campos = campos, f.camrot = camrot, f.n_filled = b->n_filled, f.fill_rs = b->fill_rs, f.slot_d = b->slot_d;
+  f.pidx = b->pidx, f.sample_p = b->sample_p, f.sample_w = b->sample_w, f.sample_dir = sample_dir;
+  f.vflag = b->vflag, f.ray_vcnt = b->ray_vcnt, f.counts = b->counts;
+  f.vec_pidx = q.K % 4 == 0 && ((uintptr_t)b->pidx & 15) == 0;
+  hipLaunchKernelGGL(k_pq_fill, dim3((unsigned)cdiv(RS, kPqKnnBlock)), dim3(kPqKnnBlock), 0, st, f);
+  PNR_LAUNCH_CHECK();
+  if (int rc = exclusive_scan(b->vflag, RS, b->counts + 0, b->valid_off, RS + 1, b->counts + 1, b->scratch,
+                              b->scratch_bytes, st, 0, nullptr, b->valid_list))
+    return rc;
+  return exclusive_scan(b->ray_vcnt, R, nullptr, b->ray_row, R + 1, b->counts + 3, b->scratch, b->scratch_bytes, st,
+                        /*as_flag=*/1);
 }
 
 extern "C" int pnr_pquery_compact(const int32_t* pidx_rows, const float* loc_rows, int64_t R, int32_t SR, int32_t K,

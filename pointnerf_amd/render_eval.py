@@ -7,10 +7,12 @@ from collections import namedtuple
 from dataclasses import dataclass
 from typing import Any, NamedTuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
 from . import querier as Q
+from . import querier_p as QP
 from .train import used_points_buffers, used_points_device
 
 
@@ -75,6 +77,8 @@ class _RenderState:
         self.used_bufs, self.used_n = None, None   # bf16: used_points_buffers for used_n points (aggregate_chunk)
         self.feat = None            # decoded features [rows, 129], reused by every call on this stream (feat_rows)
         self.feat_h = None          # bf16: the same as bf16 rows [rows, L.FEAT_H_PITCH] (feat_h_rows)
+        self.pq_build = None        # render_pixels: the perspective query's build tables (_PixelCall.prepare)
+        self.ray_hit = self.sample_dir = None   # render_pixels: the querier's ray mask, the samples' directions
 
     def _grown(self, name, rows, cols, dtype, dev):
         rows = max(int(rows), 1)
@@ -129,7 +133,8 @@ class _RenderCall:
             bufs, rays, qp = self.query_chunk(rd, rc)
             Sv, feat = self.size_chunk(bufs, r1 - r0)
             e2 = self.mark()
-            feat = self.aggregate_chunk(bufs, bufs.samples(rd, Sv, rc), feat, Sv, self.reuse_p1 or r0 > 0, p1_side)
+            s = self.samples(bufs, rd, Sv, rc)
+            feat = self.aggregate_chunk(bufs, s, feat, Sv, self.reuse_p1 or r0 > 0, p1_side)
             e3 = self.mark()
             self.composite_chunk(bufs, rays, qp, feat, Sv, r0, r1)
             self.record_chunk(ci, bufs)
@@ -143,18 +148,38 @@ class _RenderCall:
             e.record(stream)
             return e
 
+    def prepare_outputs(self):
+        """The call's output tensors, its background and its launch stream."""
+        m, dev = self.m, self.dev
+        self.C = C = m.aggregator.C          # 128 (fork) or 3 (upstream RGB head)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.out = (torch.empty((self.R, C), **f32), torch.empty((self.R, m.opt.SR), **f32),
+                    torch.empty((self.R,), **f32), torch.empty((self.R,), dtype=torch.int8, device=dev))
+        self.bg = bg_channels(self.batch.bg_color, C, dev)
+        self.launch = torch.cuda.current_stream(dev)
+
+    def prepare_tables(self):
+        """The precision's packs, the points table (camera tables set), where the counts go."""
+        m, dev = self.m, self.dev
+        self.entry, pack, extra = _AGGREGATE[self.precision]
+        self.mlp, keepw = getattr(m.aggregator, pack)()
+        self.extra, keepx = getattr(m.aggregator, extra)() if extra else (None, None)
+        self.packs = (self.mlp, keepw, self.extra, keepx)
+        self.range_flag = keepx["range_flag"] if self.precision == "fp32h2" else None
+        self.hf = self.bf16 and self.C == 128 and m.bf16_features
+        self.pts, self._keep_pts = m.neural_points.tables(self.campos, self.camrot, bf16=self.bf16)
+        self.totals = dict(S_filled=0, S_valid=0, R_hit=0, R_valid=0, n_pairs=0, n_cand=0)
+        self.caps = []
+        where = dict(pin_memory=True) if self.mode.counts == "pinned" else dict(device=dev)
+        self.counts = None if self.mode.counts == "now" else torch.empty((self.n_chunks, 8), dtype=torch.int32, **where)
+
     def prepare(self):
         """Outputs, background, camera tables, the precision's packs, the points table, where the counts go."""
         m, b, st, dev = self.m, self.batch, self.state, self.dev
         L.require_gpu(b.raydir)
         if self.force_grid:
             m.neural_points.querier.grid.key = None
-        self.C = C = m.aggregator.C          # 128 (fork) or 3 (upstream RGB head)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.out = (torch.empty((self.R, C), **f32), torch.empty((self.R, m.opt.SR), **f32),
-                    torch.empty((self.R,), **f32), torch.empty((self.R,), dtype=torch.int8, device=dev))
-        self.bg = bg_channels(b.bg_color, C, dev)
-        self.launch = torch.cuda.current_stream(dev)
+        self.prepare_outputs()
         if self.qs is not None:
             # the points can change on the launch stream (an optimizer step on xyz, a forced rebuild):
             # the query stream then waits for it before the grid build reads them
@@ -175,17 +200,7 @@ class _RenderCall:
             for t in (self.campos, self.camrot, self.ray_cam):
                 if t is not None:
                     t.record_stream(self.launch)
-        self.entry, pack, extra = _AGGREGATE[self.precision]
-        self.mlp, keepw = getattr(m.aggregator, pack)()
-        self.extra, keepx = getattr(m.aggregator, extra)() if extra else (None, None)
-        self.packs = (self.mlp, keepw, self.extra, keepx)
-        self.range_flag = keepx["range_flag"] if self.precision == "fp32h2" else None
-        self.hf = self.bf16 and C == 128 and m.bf16_features
-        self.pts, self._keep_pts = m.neural_points.tables(self.campos, self.camrot, bf16=self.bf16)
-        self.totals = dict(S_filled=0, S_valid=0, R_hit=0, R_valid=0, n_pairs=0, n_cand=0)
-        self.caps = []
-        where = dict(pin_memory=True) if self.mode.counts == "pinned" else dict(device=dev)
-        self.counts = None if self.mode.counts == "now" else torch.empty((self.n_chunks, 8), dtype=torch.int32, **where)
+        self.prepare_tables()
 
     def start_p1_side(self):
         """fp32h2: block1.0's per-point half (P1) depends on the points and weights only, so it runs on a
@@ -245,6 +260,10 @@ class _RenderCall:
             st.qring[slot] = bufs
             torch.cuda.current_stream(self.dev).wait_stream(qs)
         return bufs, rays, qp
+
+    def samples(self, bufs, rd, Sv, rc):
+        """pnr_samples of the chunk's valid samples, with room for Sv rows."""
+        return bufs.samples(rd, Sv, rc)
 
     def size_chunk(self, bufs, n_rays):
         """The chunk's feature rows (its valid samples, read now, or what the capacity allows) and their buffer."""
@@ -341,6 +360,97 @@ class _RenderCall:
         return _PendingCall(self.precision, self.caps, self.counts, self.range_flag, range_host, event, self.batch,
                             self.force_grid, self.out, m.aggregator.h2_key(), m.neural_points.querier.grid.key,
                             self.packs if self.mode is CAPTURE else ())
+
+
+# the inputs of one render_pixels call
+PixelBatch = namedtuple("PixelBatch", "campos camrot pixel_idx h w intrinsic near far bg_color")
+
+
+class _PixelCall(_RenderCall):
+    """One render_pixels call: _RenderCall's stages on the perspective query.  The rays are
+    pixels; the query is pnr_pquery_bufs on one pnr_pquery_build per call; the samples carry their own
+    directions; the composite is pnr_composite_fwd_p.  EAGER only (one counts read per chunk)."""
+
+    def __init__(self, model, precision, batch, state, events=None, reuse_p1=False):
+        self.m, self.mode, self.precision, self.batch, self.state = model, EAGER, precision, batch, state
+        self.force_grid, self.events, self.reuse_p1 = False, events, reuse_p1
+        self.capacity, self.qs, self.bf16 = None, None, False
+        self.dev, self.R = batch.pixel_idx.device, batch.pixel_idx.shape[0]
+        self.chunk = max(1, model.chunk_rays or self.R)
+        self.n_chunks = max(1, -(-self.R // self.chunk))
+
+    def prepare(self):
+        """_RenderCall.prepare, plus the cloud's perspective coordinates (NeuralPoints.w2pers, the call the
+        seam path makes, so both bin the same values) and the call's one query build."""
+        m, b, st, dev = self.m, self.batch, self.state, self.dev
+        np_, opt = m.neural_points, m.opt
+        L.require_gpu(b.pixel_idx)
+        self.prepare_outputs()
+        self.campos, self.camrot = Q.camera_tables(b.campos, b.camrot)
+        self.prepare_tables()
+        xyz = np_.xyz.detach()
+        self.pers = np_.w2pers(xyz, self.camrot[None], self.campos[None]).reshape(-1, 3).float().contiguous()
+        self.pts.pers = L.ptr(self.pers)
+        self.geo = geo = QP.frustum_geometry(opt, b.h, b.w, b.intrinsic, b.near, b.far)
+        if int(geo.dims[2]) > 65535:
+            raise L.PnrError(f"render_pixels: {int(geo.dims[2])} depth ids do not fit the query buffers (65535)")
+        self.pq = QP.pquery_params(opt, geo)
+        # the centre depth of fz = -1 (pnr_pquery's sample_loc of an unfilled slot)
+        self.z_unfilled = float(np.float32(np.float64(geo.ranges[2]) - 0.5 * np.float64(geo.scaled_vsize[2])))
+        self.qparams = L.QueryParams()
+        self.qparams.SR, self.qparams.K = int(opt.SR), int(opt.K)
+        N = self.pers.shape[0]
+        dims = (L.c_int32 * 3)(*[int(v) for v in geo.dims])
+        nb = L.c_size_t(0)
+        L.check(L.lib().pnr_pquery_scratch_bytes(N, 0, int(opt.SR), dims, L.ctypes.byref(nb)),
+                "pnr_pquery_scratch_bytes")
+        if st.pq_build is None or st.pq_build.device != dev or st.pq_build.numel() < int(nb.value):
+            st.pq_build = None
+            st.pq_build = torch.empty(-(-int(nb.value) // 16) * 16, dtype=torch.uint8, device=dev)
+        self.pq_stats = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.ray_valid = torch.zeros(self.R, dtype=torch.bool, device=dev)
+        e0 = self.mark()
+        L.check(L.lib().pnr_pquery_build(L.ctypes.byref(self.pq), L.ptr(self.pers), N, L.ptr(self.pq_stats),
+                                         L.ptr(st.pq_build), st.pq_build.numel(), L.stream_ptr(dev)),
+                "pnr_pquery_build")
+        if self.events is not None:
+            self.events.append(("build", e0, self.mark()))
+
+    def chunk_rays(self, r0, r1):
+        return self.batch.pixel_idx[r0:r1], None
+
+    def query_chunk(self, pix, rc):
+        st, dev = self.state, self.dev
+        R, SR, K = pix.shape[0], int(self.m.opt.SR), int(self.m.opt.K)
+        if st.bufs is None or not st.bufs.fits(R, SR, K) or st.bufs.counts.device != dev:
+            st.bufs = Q.QueryBuffers(R, SR, K, dev)
+        if (st.ray_hit is None or st.ray_hit.device != dev or st.ray_hit.shape[0] < max(R, 1)
+                or st.sample_dir.shape[0] < max(R * SR, 1)):
+            st.ray_hit = torch.empty(max(R, 1), dtype=torch.int8, device=dev)
+            st.sample_dir = torch.empty((max(R * SR, 1), 3), dtype=torch.float32, device=dev)
+        e0 = self.mark()
+        L.check(L.lib().pnr_pquery_bufs(L.ctypes.byref(self.pq), self.pers.shape[0], L.ptr(pix), R, L.ptr(self.campos),
+                                        L.ptr(self.camrot), L.ctypes.byref(st.bufs.c), L.ptr(st.ray_hit),
+                                        L.ptr(st.sample_dir), L.ptr(st.pq_build), st.pq_build.numel(),
+                                        L.stream_ptr(dev)), "pnr_pquery_bufs")
+        if self.events is not None:
+            self.events.append(("query", e0, self.mark()))
+        return st.bufs, None, self.qparams
+
+    def samples(self, bufs, pix, Sv, rc):
+        """The samples carry their own directions (pers2w of the centre): dirs row = sample row."""
+        return L.Samples(bufs.valid_list.data_ptr(), bufs.count_ptr(Q.COUNT_S_VALID), Sv, bufs.pidx.data_ptr(),
+                         bufs.sample_w.data_ptr(), bufs.sample_p.data_ptr(), self.state.sample_dir.data_ptr(), None,
+                         1, bufs.K, None)
+
+    def composite_chunk(self, bufs, rays, qp, feat, Sv, r0, r1):
+        cp = L.CompositeParams(float(self.geo.vsize[2]), int(self.m.opt.raydist_mode_unit), self.C, L.ptr(self.bg),
+                               max(Sv, 1))
+        L.check(L.lib().pnr_composite_fwd_p(L.ctypes.byref(qp), L.ctypes.byref(bufs.c), L.ctypes.byref(cp), r1 - r0,
+                                            L.ptr(self.state.ray_hit), self.z_unfilled, L.ptr(feat),
+                                            *(L.ptr(t[r0:r1]) for t in self.out), L.stream_ptr(self.dev)),
+                "pnr_composite_fwd_p")
+        torch.gt(bufs.ray_vcnt[:r1 - r0], 0, out=self.ray_valid[r0:r1])
 
 
 class RenderGraph:

@@ -17,14 +17,16 @@ the feature buffer) and no ``raypos[R,400,3]`` / ``[R,SR,K,38]`` intermediates.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from .aggregator import PointAggregator
 from .querier import COUNT_R_VALID, camera_tables, counts_dict, lighting_fast_querier, release_deferred
-from .querier_p import lighting_fast_querier as lighting_fast_querier_p
-from .render_eval import EAGER, QUEUED, RayBatch, RenderGraph, _RenderCall, _RenderState, bg_channels  # noqa: F401
+from .querier_p import check_sizes, lighting_fast_querier as lighting_fast_querier_p
+from .render_eval import (EAGER, QUEUED, PixelBatch, RayBatch, RenderGraph, _PixelCall, _RenderCall,  # noqa: F401
+                          _RenderState, bg_channels)
 from .render_train import TRAIN_BYTES_PER_SAMPLE, _TrainAux, _TrainCall, march_aux  # noqa: F401
 
 
@@ -211,11 +213,14 @@ class NeuralPointsRayMarching(nn.Module):
     """neural_points_volumetric_model.NeuralPointsRayMarching, fused HIP path."""
 
     def __init__(self, opt, neural_points: NeuralPoints, aggregator: PointAggregator | None = None,
-                 chunk_rays: int | None = None, precision: str = "fp32h2"):
+                 chunk_rays: int | None = None, precision: str = "fp32h2", fused_perspective: bool = False):
+        """fused_perspective: forward() of a perspective model (wcoord_query 0) renders an evaluation
+        call that wants no aux outputs through render_pixels instead of the reference-shaped seams."""
         super().__init__()
         if precision not in PRECISIONS:
             raise L.PnrError(f"precision {precision!r}: one of {PRECISIONS}")
         self.precision = precision
+        self.fused_perspective = bool(fused_perspective)
         # render_rays_train: "fp32h2" (forward chain and the weight / point-half gradient GEMMs on
         # f16-split MFMA, fp32-accurate: the measured default), "fp32x3" (split-bf16 MFMA,
         # fp32-accurate) or "fp32" (native fp32 MFMA)
@@ -253,6 +258,7 @@ class NeuralPointsRayMarching(nn.Module):
         self.last_train_aux = None    # _TrainAux of the last render_rays_train
         self._budget_dev = None       # a quarter of the device's memory, once asked for (render_train.train_budget)
         self._rw2c_key = None
+        self._pixel_ray_valid = None
         if getattr(opt, "which_render_func", "radiance") != "radiance" or \
                 getattr(opt, "which_blend_func", "alpha") != "alpha" or \
                 getattr(opt, "which_tonemap_func", "off") != "off":
@@ -260,8 +266,8 @@ class NeuralPointsRayMarching(nn.Module):
 
     def _world_only(self, who: str):
         if self.neural_points.perspective:
-            raise L.PnrError(f"{who}: the fused frame is world-query only; call the module (forward) with "
-                             "wcoord_query 0")
+            raise L.PnrError(f"{who}: the fused frame is world-query only; with wcoord_query 0 call render_pixels "
+                             "(an evaluation frame) or the module (forward)")
 
     def _sync_rw2c(self):
         """The aggregator renders with NeuralPoints.Rw2c (neural_points.py:289;
@@ -342,6 +348,61 @@ class NeuralPointsRayMarching(nn.Module):
             if events is not None:
                 del events[n_ev:]
             out, _ = self._render_rays(EAGER, "fp32x3", batch, self._state, **opts)
+        return out
+
+    @torch.no_grad()
+    def render_pixels(self, campos, camrotc2w, pixel_idx, h, w, intrinsic, near, far, bg_color, events=None,
+                      reuse_p1=False):
+        """The fused evaluation frame of a perspective model (wcoord_query 0): pnr_pquery_build
+        once, then per chunk of chunk_rays pixels pnr_pquery_bufs -> the precision's aggregate over the valid
+        samples -> pnr_composite_fwd_p.  No gathered pair tensor, one host read (the counts) per chunk.
+        pixel_idx: [R,2] (x, y), or None for the whole h x w frame in row-major order.  Returns render_rays'
+        (ray_color [R,C], opacity [R,SR], is_bg [R], ray_mask [R] int8) and sets last_counts; ray_mask is the
+        querier's (a hit ray without any neighbour keeps 1 and composites to the background).  One camera per
+        call.  It never applies shpnt_jitter (the sample depths are the voxel centres).  events, reuse_p1 and
+        the fp32h2 fallback to fp32x3 as in render_rays; events also receives the ("build", ...) stage."""
+        np_, opt = self.neural_points, self.opt
+        if not np_.perspective:
+            raise L.PnrError("render_pixels renders the perspective query (wcoord_query 0); this model queries the "
+                             "world grid: call render_rays")
+        if self.precision == "bf16":
+            raise L.PnrError("render_pixels: precision 'bf16' is not supported (fp32, fp32x3 or fp32h2)")
+        if int(opt.K) > 8:
+            raise L.PnrError(f"render_pixels: K = {int(opt.K)} neighbours per sample; the fused aggregate takes "
+                             "1 .. 8")
+        if getattr(opt, "inverse", 0):
+            raise L.PnrError("--inverse 1 (disparity ray generation) is not supported")
+        if int(opt.NN) <= 0:
+            raise L.PnrError("NN == 0 (query_rand_along_ray: a reservoir seeded by time()) is not supported")
+        check_sizes(opt)
+        if self._pending:
+            self._done = self.finish() + self._done
+        self._sync_rw2c()
+        dev = np_.xyz.device
+        h = int(h.reshape(-1)[0].item()) if torch.is_tensor(h) else int(h)
+        w = int(w.reshape(-1)[0].item()) if torch.is_tensor(w) else int(w)
+        intr = intrinsic.detach().cpu().numpy() if torch.is_tensor(intrinsic) else intrinsic
+        near = float(torch.min(near).item()) if torch.is_tensor(near) else float(near)
+        far = float(torch.max(far).item()) if torch.is_tensor(far) else float(far)
+        if pixel_idx is None:
+            ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.int32, device=dev),
+                                    torch.arange(w, dtype=torch.int32, device=dev), indexing="ij")
+            pix = torch.stack([xs, ys], -1).reshape(-1, 2).contiguous()
+        else:
+            pix = pixel_idx.to(dev).reshape(-1, 2).to(torch.int32).contiguous()
+        batch = PixelBatch(campos, camrotc2w, pix, h, w, np.asarray(intr, np.float32).reshape(-1, 3, 3)[0], near, far,
+                           bg_color)
+        prec = self._precision_now()
+        n_ev = len(events) if events is not None else 0
+        call = _PixelCall(self, prec, batch, self._state, events=events, reuse_p1=reuse_p1)
+        out, _ = call.run()
+        if prec == "fp32h2" and not self.aggregator.h2_range_ok():
+            self._block_h2()
+            if events is not None:
+                del events[n_ev:]
+            call = _PixelCall(self, "fp32x3", batch, self._state, events=events)
+            out, _ = call.run()
+        self._pixel_ray_valid = call.ray_valid   # [R] bool: the ray has a valid sample (forward's queried_shading)
         return out
 
     def _render_rays(self, mode, precision, batch, state, **options):
@@ -668,6 +729,35 @@ class NeuralPointsRayMarching(nn.Module):
                 out["coarse_raycolor"].reshape(1, img_h, img_w, -1)).reshape(1, -1, 3)
         return out
 
+    def _fused_forward_applies(self, bg_color=None) -> bool:
+        """forward() may take render_pixels: no training step under way, no probe, no aux output wanted,
+        and no sample jitter to apply (render_pixels never jitters)."""
+        train = torch.is_grad_enabled() and self.training and (
+            any(p.requires_grad for p in self.parameters()) or (torch.is_tensor(bg_color) and bg_color.requires_grad))
+        opt = self.opt
+        jitter_free = getattr(opt, "is_train", 0) == 0 or getattr(opt, "shpnt_jitter", "passfunc") == "passfunc"
+        return not train and getattr(opt, "prob", 0) != 1 and not self.wants_aux() and jitter_free
+
+    def _forward_pixels(self, campos, bg_color, camrotc2w, pixel_idx, near, far, h, w, intrinsic):
+        """_forward_perspective's dict from render_pixels (fused_perspective)."""
+        for name, v in (("pixel_idx", pixel_idx), ("h", h), ("w", w), ("intrinsic", intrinsic)):
+            if v is None:
+                raise L.PnrError(f"forward with wcoord_query 0 (the perspective query) needs {name}")
+        color, opacity, is_bg, ray_mask = self.render_pixels(campos, camrotc2w, pixel_idx, h, w, intrinsic, near, far,
+                                                             bg_color)
+        R = color.shape[0]
+        shading = 1 - self._pixel_ray_valid.float().view(1, R, 1)   # 1 - (the ray has a valid sample)
+        out = dict(coarse_raycolor=color.view(1, R, -1), coarse_point_opacity=opacity.view(1, R, -1),
+                   coarse_is_background=is_bg.view(1, R, 1), ray_mask=ray_mask.view(1, R))
+        out["coarse_mask"] = 1 - out["coarse_is_background"]
+        out["queried_shading"] = shading.repeat(1, 1, 3)
+        if self.neural_render_2d is not None:
+            img_h = int(h.item()) if torch.is_tensor(h) else int(h)
+            img_w = int(w.item()) if torch.is_tensor(w) else int(w)
+            out["final_coarse_raycolor"] = self.neural_render_2d(
+                out["coarse_raycolor"].reshape(1, img_h, img_w, -1)).reshape(1, -1, 3)
+        return out
+
     def forward(self, campos, raydir, gt_image=None, bg_color=None, camrotc2w=None, pixel_idx=None,
                 near=None, far=None, focal=None, h=None, w=None, intrinsic=None, **kargs):
         """neural_points_volumetric_model.py:272-352 (+ fill_invalid :354-389);
@@ -680,6 +770,8 @@ class NeuralPointsRayMarching(nn.Module):
         if "bg_ray" in kargs:
             bg_color = None
         if self.neural_points.perspective:
+            if self.fused_perspective and self._fused_forward_applies(bg_color):
+                return self._forward_pixels(campos, bg_color, camrotc2w, pixel_idx, near, far, h, w, intrinsic)
             return self._forward_perspective(campos, raydir, gt_image, bg_color, camrotc2w, pixel_idx, near, far,
                                              focal, h, w, intrinsic)
         # training loop (model(...) then loss.backward(), as run/train_ft.py does):

@@ -6,7 +6,13 @@ query apart) of the same cloud and the same number of rays.  HIP events,
 warm-up, median of --repeats.  Prints one JSON line with the call times, the
 query's stats, the bytes its kernels must move (computed from the shapes) and
 the shader clock under load.  Per-kernel times: run it under
-`rocprofv3 --kernel-trace --stats` with --repeats 5."""
+`rocprofv3 --kernel-trace --stats` with --repeats 5.
+
+--frame times the whole evaluation frame on the same inputs instead (DESIGN.md
+29): render_pixels (the fused perspective frame) for fp32 and fp32h2, with its
+stage events, next to the module's seam forward in eval mode -- the same
+timing rule -- and the peak device memory of each
+(torch.cuda.max_memory_allocated).  --out writes the JSON to a file as well."""
 import argparse
 import json
 import os
@@ -40,6 +46,69 @@ def timed(fn, warmup, repeats):
     return round(times[len(times) // 2], 3), round(times[0], 3), round(times[-1], 3)
 
 
+def frame_bench(a, dev, opt, xyz, cp, cr, K, pix):
+    """render_pixels (fp32, fp32h2) and the seam forward on one frame -> dict."""
+    from pointnerf_amd.aggregator import PointAggregator
+    from pointnerf_amd.renderer import NeuralPoints, NeuralPointsRayMarching
+    W, H, N = a.width, a.height, a.points
+    torch.manual_seed(0)
+    emb, color, dirs, conf = S.point_features(N, seed=0)
+    agg = PointAggregator(opt).to(dev).eval()
+    np_ = NeuralPoints(opt, dev, xyz, emb, color, dirs, conf)
+    bg = torch.rand(agg.C, generator=torch.Generator().manual_seed(1)).to(dev)
+    args = (cp, cr, pix, H, W, K, opt.near_plane, opt.far_plane, bg)
+    res = {"points": N, "frame": [W, H], "rays": W * H, "hip_ms": {}, "stage_ms": {}, "peak_MB": {}, "counts": {},
+           "lib": os.path.basename(L.LIB_PATH), "warmup": a.warmup, "repeats": a.repeats}
+    outs = {}
+    for prec in ("fp32", "fp32h2"):
+        m = NeuralPointsRayMarching(opt, np_, agg, precision=prec)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        base = torch.cuda.memory_allocated(dev)
+        with torch.no_grad():
+            res["hip_ms"][f"render_pixels {prec}"] = timed(lambda: m.render_pixels(*args), a.warmup, a.repeats)
+            peak = torch.cuda.max_memory_allocated(dev) - base
+            res["peak_MB"][f"render_pixels {prec}"] = round(peak / 1e6, 1)
+            stages = {}
+            for _ in range(a.repeats):
+                ev = []
+                outs[prec] = m.render_pixels(*args, events=ev)
+                torch.cuda.synchronize()
+                for name, e0, e1 in ev:
+                    stages.setdefault(name, []).append(e0.elapsed_time(e1))
+        res["stage_ms"][prec] = {k: round(sorted(v)[len(v) // 2], 3) for k, v in stages.items()}
+        res["counts"][prec] = dict(m.last_counts, h2_fallbacks=m.h2_fallbacks)
+        del m
+    a32, ah2 = outs["fp32"], outs["fp32h2"]
+    res["fp32h2_vs_fp32_max_abs"] = {"ray_color": float((a32[0] - ah2[0]).abs().max()),
+                                     "opacity": float((a32[1] - ah2[1]).abs().max())}
+    # the seam forward of the same model (NeuralPoints.forward's gathers, PointAggregator.forward, torch march)
+    m = NeuralPointsRayMarching(opt, np_, agg, precision="fp32").eval()
+    raydir = torch.from_numpy(S.pixel_rays(H, W, float(K[0, 0]), cr.cpu().numpy())).to(dev)
+    t = lambda v: torch.tensor([[v]], device=dev)   # noqa: E731
+    inp = dict(campos=cp[None], raydir=raydir[None], bg_color=bg, camrotc2w=cr[None],
+               pixel_idx=pix[None].long(),
+               near=t(opt.near_plane), far=t(opt.far_plane), h=torch.tensor([H], device=dev),
+               w=torch.tensor([W], device=dev), intrinsic=torch.from_numpy(K).to(dev)[None])
+    seam_out = {}
+
+    def seam():
+        seam_out["o"] = None   # the previous frame's tensors are freed before the next one's are allocated
+        seam_out["o"] = m(**inp)
+
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    base = torch.cuda.memory_allocated(dev)
+    with torch.no_grad():
+        res["hip_ms"]["seam forward (eval)"] = timed(seam, a.warmup, a.repeats)
+    res["peak_MB"]["seam forward (eval)"] = round((torch.cuda.max_memory_allocated(dev) - base) / 1e6, 1)
+    o = seam_out["o"]
+    res["fused_vs_seam_max_abs"] = {"ray_color": float((a32[0] - o["coarse_raycolor"][0]).abs().max()),
+                                    "opacity": float((a32[1] - o["coarse_point_opacity"][0]).abs().max()),
+                                    "ray_mask_equal": bool(torch.equal(a32[3], o["ray_mask"][0]))}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=1000000)
@@ -48,6 +117,8 @@ def main():
     ap.add_argument("--scale", type=float, default=0.6, help="cloud scale: depths 3.3 .. 4.7 from the radius-4 camera")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--frame", action="store_true", help="time the whole frame: render_pixels and the seam forward")
+    ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     W, H, N = a.width, a.height, a.points
@@ -62,6 +133,8 @@ def main():
     px, py = np.meshgrid(np.arange(W, dtype=np.int32), np.arange(H, dtype=np.int32))
     pix = torch.from_numpy(np.stack([px, py], -1).reshape(-1, 2)).to(dev)
     R, SR, Kn = W * H, opt.SR, opt.K
+    if a.frame:
+        return emit(frame_bench(a, dev, opt, xyz, cp, cr, K, pix), a.out)
 
     q = lighting_fast_querier(dev, opt)
     seam = lambda: q.query_points(pix[None], pers[None], xyz[None], None, H, W, K, opt.near_plane, opt.far_plane,  # noqa: E731
@@ -126,7 +199,15 @@ def main():
     res["world"] = {"counts": bufs.read_counts(), "grid": wq.grid.stats()}
     res["hip_ms"]["world query (grid cached)"] = timed(world_query, a.warmup, a.repeats)
     res["hip_ms"]["world grid build"] = timed(lambda: wq.grid.build(wopt, xyz, force=True), a.warmup, a.repeats)
-    print(json.dumps(res, default=lambda o: o.tolist() if hasattr(o, "tolist") else str(o)))
+    emit(res, a.out)
+
+
+def emit(res, out):
+    line = json.dumps(res, default=lambda o: o.tolist() if hasattr(o, "tolist") else str(o))
+    print(line)
+    if out:
+        with open(out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
