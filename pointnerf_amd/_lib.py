@@ -522,3 +522,11 @@ def weighted_colsum(w: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     check(lib().pnr_weighted_colsum(ptr(w), ptr(x), w.numel(), C, ptr(out), ptr(part), stream_ptr(x.device)),
           "pnr_weighted_colsum")
     return out
+
+
+def host_scalar(v, kind=float, reduce=None):
+    """A caller's near / far / h / w as the Python number the host layer works with: a tensor is read here
+    (reduce: torch.min / torch.max of a [..] near / far, else its first element), a number passes through."""
+    if torch.is_tensor(v):
+        v = (reduce(v) if reduce is not None else v.reshape(-1)[0]).item()
+    return kind(v)

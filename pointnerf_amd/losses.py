@@ -21,6 +21,7 @@ import math
 import torch
 
 from . import _lib as L
+from .querier import COUNT_R_VALID
 
 # item-name prefixes of compute_losses (:543, :552, :564) -> index into color_losses' values
 PLAIN, MASKED, MISS, DEPTH_MASKED = 0, 1, 2, 3
@@ -149,6 +150,40 @@ class _SparseConfLoss(torch.autograd.Function):
         L.check(L.lib().pnr_sparse_loss_bwd(L.ptr(wfix), L.ptr(c), c.numel(), L.ptr(state), L.ptr(g), L.ptr(d),
                                             L.stream_ptr(c.device)), "pnr_sparse_loss_bwd")
         return d.reshape(ctx.conf_shape), None, None, None
+
+
+class _ZeroOneConfLoss(torch.autograd.Function):
+    """NeuralPointsRayMarching.zero_one_conf_loss on libpnr: the per-point entry
+    counts of the query's neighbour lists (pnr_point_counts), then one fused
+    reduction (pnr_zero_one_loss_fwd) and one backward kernel -- the same value
+    and gradient as torch's clamp / log / mean over the gathered [1, R'', SR, K]
+    conf_coefficient, in three launches and without host reads."""
+
+    @staticmethod
+    def forward(ctx, conf, bufs, SR, K, eps):
+        dev = conf.device
+        N = conf.numel()
+        c = conf.detach().float().contiguous()
+        counts = torch.zeros(N, dtype=torch.float32, device=dev)
+        L.check(L.lib().pnr_point_counts(L.ptr(bufs.pidx), L.ptr(bufs.counts), K, bufs.pidx.numel() // K,
+                                         L.ptr(counts), L.stream_ptr(dev)), "pnr_point_counts")
+        part = torch.empty(1024, dtype=torch.float32, device=dev)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        L.check(L.lib().pnr_zero_one_loss_fwd(L.ptr(c), L.ptr(counts), N, L.c_void_p(bufs.count_ptr(COUNT_R_VALID)),
+                                              SR * K, eps, L.ptr(part), L.ptr(out), L.stream_ptr(dev)),
+                "pnr_zero_one_loss_fwd")
+        ctx.save_for_backward(c, counts, out)
+        ctx.eps = eps
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        c, counts, out = ctx.saved_tensors
+        d = torch.empty_like(c)
+        g = g.reshape(1).float().contiguous()
+        L.check(L.lib().pnr_zero_one_loss_bwd(L.ptr(c), L.ptr(counts), c.numel(), ctx.eps, L.ptr(out), L.ptr(g),
+                                              L.ptr(d), L.stream_ptr(c.device)), "pnr_zero_one_loss_bwd")
+        return d, None, None, None, None
 
 
 def sparse_loss(weight, conf_coefficient):

@@ -39,13 +39,26 @@ def check_sizes(opt):
                          "then depends on the other rays of the batch, which is not reproduced")
 
 
+def check_supported(opt):
+    """What every entry of the perspective query refuses (the querier, frustum_geometry, render_pixels),
+    stated once."""
+    if getattr(opt, "inverse", 0):
+        raise L.PnrError("--inverse 1 (disparity ray generation) is not supported")
+    if int(getattr(opt, "NN", 2)) <= 0:
+        raise L.PnrError("NN == 0 (query_rand_along_ray: a reservoir seeded by time()) is not supported")
+    check_sizes(opt)
+    jitter = getattr(opt, "shpnt_jitter", "passfunc")
+    if jitter not in JITTERS:
+        raise L.PnrError(f"shpnt_jitter {jitter!r}: one of {JITTERS}")
+    return jitter
+
+
 def frustum_geometry(opt, h, w, intrinsic, near_depth, far_depth):
     """get_hyperparameters (query_point_indices.py:52-75) in numpy with the
     reference's promotions for an fp32 intrinsic and fp32 depths: ranges,
     vsize, vdim, vscale, dims (scaled_vdim), scaled_vsize, ray_vsize,
     radius_limit, depth_limit."""
-    if getattr(opt, "inverse", 0):
-        raise L.PnrError("--inverse 1 (disparity ray generation) is not supported")
+    check_supported(opt)
     k = np.asarray(intrinsic, dtype=np.float32).reshape(3, 3)
     h, w = int(np.asarray(h).reshape(-1)[0]), int(np.asarray(w).reshape(-1)[0])
     near, far = np.float32(np.asarray(near_depth).reshape(-1)[0]), np.float32(np.asarray(far_depth).reshape(-1)[0])
@@ -92,12 +105,8 @@ class lighting_fast_querier:  # noqa: N801  (reference class name)
             raise L.PnrError("lighting_fast_querier needs a cuda (ROCm) device")
         self.gpu = self.device.index or 0
         self.opt = opt
+        check_supported(opt)
         self.inverse = getattr(opt, "inverse", 0)
-        if self.inverse:
-            raise L.PnrError("--inverse 1 (disparity ray generation) is not supported")
-        if getattr(opt, "NN", 2) <= 0:
-            raise L.PnrError("NN == 0 (query_rand_along_ray: a reservoir seeded by time()) is not supported")
-        check_sizes(opt)
         self.count = 0
         self.last_slot_z = None     # [R',SR] int32: the depth ids of the last call's samples
         self._stats_dev = None
@@ -122,14 +131,7 @@ class lighting_fast_querier:  # noqa: N801  (reference class name)
         no neighbour).  B must be 1."""
         L.require_gpu(point_xyz_pers_tensor)
         opt = self.opt
-        if getattr(opt, "inverse", 0):
-            raise L.PnrError("--inverse 1 (disparity ray generation) is not supported")
-        if opt.NN <= 0:
-            raise L.PnrError("NN == 0 (query_rand_along_ray: a reservoir seeded by time()) is not supported")
-        check_sizes(opt)
-        jitter = getattr(opt, "shpnt_jitter", "passfunc")
-        if jitter not in JITTERS:
-            raise L.PnrError(f"shpnt_jitter {jitter!r}: one of {JITTERS}")
+        jitter = check_supported(opt)
         if point_xyz_pers_tensor.dim() == 3 and point_xyz_pers_tensor.shape[0] != 1:
             raise L.PnrError("batch size B > 1 is not supported (the reference uses B = 1)")
         for name, v in (("pixel_idx", pixel_idx_tensor), ("h", h), ("w", w), ("intrinsic", intrinsic)):
@@ -137,8 +139,7 @@ class lighting_fast_querier:  # noqa: N801  (reference class name)
                 raise L.PnrError(f"perspective query (wcoord_query 0) needs {name}")
         dev = point_xyz_pers_tensor.device
         intr = intrinsic.detach().cpu().numpy() if torch.is_tensor(intrinsic) else np.asarray(intrinsic)
-        h = h.item() if torch.is_tensor(h) else h
-        w = w.item() if torch.is_tensor(w) else w
+        h, w = L.host_scalar(h, int), L.host_scalar(w, int)
         geo = frustum_geometry(opt, h, w, intr.reshape(-1, 3, 3)[0], near_depth, far_depth)
         qp = pquery_params(opt, geo)
         pers = point_xyz_pers_tensor.detach().reshape(-1, 3).float().contiguous()

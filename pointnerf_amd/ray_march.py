@@ -10,6 +10,9 @@ neural_points_volumetric_model.py:314): ``RayMarchFn`` runs the forward on
 every output: ray_color, opacity, acc_transmission, blend_weight,
 background_transmission) plus ``pnr_weighted_colsum`` for d bg_color, which the
 fork optimises (mvs_points_volumetric_model.py:92-94).
+
+``perspective_ray_dist``, ``march_hit_rays`` and ``fill_invalid`` are the rest of
+the perspective seam forward around it, plain torch on any device.
 """
 from __future__ import annotations
 
@@ -115,3 +118,52 @@ def ray_march(ray_dist, ray_valid, ray_features, render_func=radiance_render, bl
     # background_blend_weight = blend_func(1, background_transmission)
     return (color.view(B, R, C), ray_features[..., 1:], opacity.view(B, R, SR), acc_T.view(B, R, SR),
             blend_w.view(B, R, SR, 1), bgT, bgT)
+
+
+# The seam forward of a perspective model (neural_points_volumetric_model.py:288-341 and fill_invalid
+# :354-389) around ray_march, as plain torch on whichever device the tensors live: the statement of
+# what pnr_composite_fwd_p computes.
+def perspective_ray_dist(sample_z, ray_valid, vz: float, unit: int):
+    """ray_dist of the hit rays [1,R',SR] from their samples' depths: the step to the next slot's depth
+    (running maximum, so the unfilled slots at z_unfilled add nothing), the last slot's step vz; a step
+    below 1e-8 -- and with raydist_mode_unit one above 2 vz -- becomes vz; an invalid sample's is 0."""
+    rd = torch.cummax(sample_z, dim=-1)[0]
+    rd = torch.cat([rd[..., 1:] - rd[..., :-1], torch.full(rd.shape[:2] + (1,), vz, device=rd.device)], dim=-1)
+    m = rd < 1e-8
+    if unit > 0:
+        m = torch.logical_or(m, rd > 2 * vz)
+    m = m.to(torch.float32)
+    return (rd * (1.0 - m) + m * vz) * ray_valid.float()
+
+
+def march_hit_rays(ray_dist, ray_valid, feats, bg_color):
+    """(color [1,R',C], opacity [1,R',SR], blend_weight [1,R',SR,1], bg_T [1,R',1]) of ray_march; no ray
+    hit: empty tensors, fill_invalid then writes every row."""
+    if ray_dist.shape[1] == 0:
+        f32 = dict(dtype=torch.float32, device=ray_dist.device)
+        SR = ray_dist.shape[2]
+        return (torch.zeros((1, 0, feats.shape[-1] - 1), **f32), torch.zeros((1, 0, SR), **f32),
+                torch.zeros((1, 0, SR, 1), **f32), torch.zeros((1, 0, 1), **f32))
+    color, _, opacity, _, blend_weight, bg_T, _ = ray_march(ray_dist, ray_valid, feats, radiance_render, alpha_blend,
+                                                            bg_color)
+    return color, opacity, blend_weight, bg_T
+
+
+def fill_invalid(ray_mask, color, opacity, bg_T, ray_valid, bg_color):
+    """fill_invalid (:354-389): the hit rays' rows scattered into all R rays of ray_mask [1,R]; a missed
+    ray gets the background colour, opacity 0 and background transmission 1.  Returns (color [1,R,C],
+    opacity [1,R,SR], is_bg [1,R,1], any_valid [R] bool: the ray has a valid sample)."""
+    B, R = ray_mask.shape
+    dev = color.device
+    hit = ray_mask[0] > 0
+    C = color.shape[-1]
+    bg = torch.zeros(C, device=dev) if bg_color is None else bg_color.to(dev).float().reshape(-1)
+    full_color = (torch.ones((B, R, C), dtype=color.dtype, device=dev) * bg[None, None, :])
+    full_color[:, hit] = color
+    full_bg = torch.ones((B, R, 1), dtype=bg_T.dtype, device=dev)
+    full_bg[:, hit] = bg_T
+    full_op = torch.zeros((B, R, opacity.shape[2]), dtype=opacity.dtype, device=dev)
+    full_op[:, hit] = opacity
+    any_valid = torch.zeros(R, dtype=torch.bool, device=dev)
+    any_valid[hit] = torch.any(ray_valid, dim=-1)[0]
+    return full_color, full_op, full_bg, any_valid

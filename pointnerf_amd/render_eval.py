@@ -1,5 +1,6 @@
 """Host layer of the evaluation render: a render_rays / finish() / RenderGraph call as stages over
-the ray chunks, issuing kernels, events and stream waits in one fixed order; the typed records the calls leave."""
+the ray chunks, issuing kernels, events and stream waits in one fixed order; the typed records the calls leave;
+the queue of sync=False calls and the fp32h2 fallback the module's entry points share."""
 from __future__ import annotations
 
 import gc
@@ -25,6 +26,13 @@ def bg_channels(bg_color, C: int, dev):
     if bg.numel() not in (1, C):
         raise L.PnrError(f"bg_color must have 1 or {C} channels")
     return bg if bg.numel() == C else bg.expand(C).contiguous()
+
+
+def query_params(SR, K) -> L.QueryParams:
+    """The pnr_query_params of the kernels that only walk query buffers: their SR and K."""
+    qp = L.QueryParams()
+    qp.SR, qp.K = int(SR), int(K)
+    return qp
 
 
 # the inputs of one render call, as the caller gave them
@@ -59,6 +67,106 @@ class _PendingCall:
     h2_key: tuple       # what a re-render must find unchanged: the weights ...
     grid_key: Any       # ... and the grid
     keep: tuple = ()    # CAPTURE: the packs the captured launches point into
+
+
+def chunk_counts(rec: _PendingCall):
+    """(feature rows the chunk was sized for, its rays, its counts dict) per chunk of a completed call."""
+    for (cap, rays), h in zip(rec.caps, rec.counts.tolist()):
+        yield cap, rays, Q.counts_dict(h, n_used=False)
+
+
+class _CallQueue:
+    """The render_rays(sync=False) calls of one module that await finish(), and what sizes the next one.
+    It holds no reference to the module (the two would form a cycle and the module's device memory would
+    wait for a cyclic collection): the module passes itself to flush / finish."""
+
+    def __init__(self):
+        self.pending = []        # _PendingCall records, in issue order
+        self.done = []           # counts of calls a synchronous render completed, for the next finish()
+        self.sv_per_ray = None   # largest valid samples per ray seen (feature-buffer sizing)
+
+    def observe(self, counts, rays):
+        r = counts["S_valid"] / max(rays, 1)
+        self.sv_per_ray = r if self.sv_per_ray is None else max(self.sv_per_ray, r)
+
+    def flush(self, m):
+        """Before a call that reads (and may clear) the shared range flag and the counts: complete the pending
+        calls so none of their checks is lost; their counts stay queued for the caller's next finish()."""
+        if self.pending:
+            self.done = self.finish(m) + self.done
+
+    def finish(self, m, upto=None):
+        """NeuralPointsRayMarching.finish of module m."""
+        if upto is None:   # freeing a collected GridHandle synchronises the device: not while later calls stay queued
+            Q.release_deferred()
+        done = self.done
+        n_all = len(done) + len(self.pending)
+        k = n_all if upto is None else min(int(upto), n_all)
+        need = k - len(done)
+        if need > 0:
+            head = self.pending[:need]
+            head[-1].event.synchronize()
+            # the range flags as copied to pinned memory behind each call's event (a
+            # .item() here would queue behind -- and wait for -- the later calls)
+            if need < len(self.pending) and any(int(r.range_host[0]) != 0 for r in head if r.range_flag is not None):
+                head = self.pending
+                head[-1].event.synchronize()
+            self.pending = self.pending[len(head):]
+            done = done + self.complete(m, head)
+        self.done = done[k:]
+        return done[:k]
+
+    def complete(self, m, pend):
+        """finish()'s checks on calls whose last kernels have completed."""
+        # every fp32h2 call's own range flag (the packs, and their flag, are rebuilt when the weights change between
+        # calls), read from the call's pinned copy taken after its launches: the raised ones, by storage
+        h2 = [r for r in pend if r.range_flag is not None]
+        raised = {r.range_flag.data_ptr(): r.range_flag for r in h2 if int(r.range_host[0]) != 0}
+        if raised:
+            cur = m.aggregator.h2_key()
+            for f in raised.values():
+                f.zero_()
+            m.aggregator.h2_reset_range()
+            if any(r.h2_key == cur for r in h2):
+                m._h2_blocked_key = cur
+            m.h2_fallbacks += 1
+        counts = []
+        for rec in pend:
+            tot = dict(S_filled=0, S_valid=0, R_hit=0, R_valid=0, n_pairs=0, n_cand=0)
+            over = False
+            for cap, rays, c in chunk_counts(rec):
+                self.observe(c, rays)
+                over |= c["S_valid"] > cap
+                for k in tot:
+                    tot[k] += c[k]
+            rec_bad = rec.range_flag is not None and rec.range_flag.data_ptr() in raised
+            if over or rec_bad:
+                if rec.h2_key != m.aggregator.h2_key() or rec.grid_key != m.neural_points.querier.grid.key:
+                    raise L.PnrError("a render_rays(sync=False) call must be re-rendered, but the weights or the "
+                                     "points changed before finish(): call finish() before modifying the model")
+                out, _ = m._render_rays(EAGER, "fp32x3" if rec_bad else rec.precision, rec.batch, m._state,
+                                        force_grid=rec.force_grid)
+                for dst, src in zip(rec.out, out):
+                    dst.copy_(src)
+                tot = dict(m.last_counts)
+                m.overflow_rerenders += int(over)
+            counts.append(tot)
+        m.last_counts = counts[-1]
+        return counts
+
+
+def with_h2_fallback(model, precision, events, run):
+    """run(precision, first) -> outputs, once; a fp32h2 run whose activations left the f16 range (the
+    launches' range flag, one 4-byte read) blocks h2 for these weights, drops the events the run appended
+    and runs again on fp32x3 (first False: without the caller's reuse_p1)."""
+    n_ev = len(events) if events is not None else 0
+    out = run(precision, True)
+    if precision == "fp32h2" and not model.aggregator.h2_range_ok():
+        model._block_h2()
+        if events is not None:
+            del events[n_ev:]
+        out = run("fp32x3", False)
+    return out
 
 
 class _RenderState:
@@ -271,7 +379,7 @@ class _RenderCall:
             cnt = bufs.read_counts()
             for k in self.totals:
                 self.totals[k] += cnt[k]
-            self.m._observe(cnt, n_rays)
+            self.m._queue.observe(cnt, n_rays)
             Sv = cnt["S_valid"]
         else:
             Sv = min(int(n_rays * self.capacity) + 1024, n_rays * self.m.opt.SR)
@@ -362,8 +470,25 @@ class _RenderCall:
                             self.packs if self.mode is CAPTURE else ())
 
 
-# the inputs of one render_pixels call
-PixelBatch = namedtuple("PixelBatch", "campos camrot pixel_idx h w intrinsic near far bg_color")
+class PixelBatch(namedtuple("PixelBatch", "campos camrot pixel_idx h w intrinsic near far bg_color")):
+    """The inputs of one render_pixels call: pixel_idx int32 [R,2] on the device, h / w ints, intrinsic a
+    numpy fp32 [3,3], near / far floats."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, dev, campos, camrot, pixel_idx, h, w, intrinsic, near, far, bg_color):
+        """From a caller's arguments: tensors or numbers for h / w / near / far, the first intrinsic of a
+        batch, and pixel_idx None for the whole h x w frame in row-major order."""
+        h, w = L.host_scalar(h, int), L.host_scalar(w, int)
+        intr = intrinsic.detach().cpu().numpy() if torch.is_tensor(intrinsic) else intrinsic
+        if pixel_idx is None:
+            ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.int32, device=dev),
+                                    torch.arange(w, dtype=torch.int32, device=dev), indexing="ij")
+            pix = torch.stack([xs, ys], -1).reshape(-1, 2).contiguous()
+        else:
+            pix = pixel_idx.to(dev).reshape(-1, 2).to(torch.int32).contiguous()
+        return cls(campos, camrot, pix, h, w, np.asarray(intr, np.float32).reshape(-1, 3, 3)[0],
+                   L.host_scalar(near, float, torch.min), L.host_scalar(far, float, torch.max), bg_color)
 
 
 class _PixelCall(_RenderCall):
@@ -397,8 +522,7 @@ class _PixelCall(_RenderCall):
         self.pq = QP.pquery_params(opt, geo)
         # the centre depth of fz = -1 (pnr_pquery's sample_loc of an unfilled slot)
         self.z_unfilled = float(np.float32(np.float64(geo.ranges[2]) - 0.5 * np.float64(geo.scaled_vsize[2])))
-        self.qparams = L.QueryParams()
-        self.qparams.SR, self.qparams.K = int(opt.SR), int(opt.K)
+        self.qparams = query_params(opt.SR, opt.K)
         N = self.pers.shape[0]
         dims = (L.c_int32 * 3)(*[int(v) for v in geo.dims])
         nb = L.c_size_t(0)
@@ -415,6 +539,11 @@ class _PixelCall(_RenderCall):
                 "pnr_pquery_build")
         if self.events is not None:
             self.events.append(("build", e0, self.mark()))
+
+    def run(self):
+        """_RenderCall.run; the outputs end with ray_valid ([R] bool: the ray has a valid sample)."""
+        out, rec = super().run()
+        return out + (self.ray_valid,), rec
 
     def chunk_rays(self, r0, r1):
         return self.batch.pixel_idx[r0:r1], None
@@ -526,8 +655,8 @@ class RenderGraph:
         """True when the last replay's outputs are valid: every chunk's valid samples fit the captured
         feature buffer and (fp32h2) no activation left the f16 range.  Synchronises."""
         ok = True
-        for (cap, _rays), h in zip(self.rec.caps, self.rec.counts.tolist()):
-            self.last_counts = c = Q.counts_dict(h, n_used=False)
+        for cap, _rays, c in chunk_counts(self.rec):
+            self.last_counts = c
             ok &= c["S_valid"] <= cap
         if self.precision == "fp32h2" and not self.model.aggregator.h2_range_ok():
             self.model.aggregator.h2_reset_range()

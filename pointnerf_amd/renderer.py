@@ -1,163 +1,48 @@
-"""Neural point cloud + the fused render module (the north-star hot path).
-
-``NeuralPoints`` mirrors the parameter table of
-models/neural_points/neural_points.py:11-331 (same parameter names, so the
-``neural_points.*`` keys of a reference checkpoint load into it) and its
-14-tuple ``forward`` (neural_points.py:782-812) for API compatibility.
+"""The render module (the north-star hot path; its host layer: DESIGN.md 30).
 
 ``NeuralPointsRayMarching`` mirrors
 models/neural_points_volumetric_model.py:230-389 (forward(**input) -> dict with
 coarse_raycolor / coarse_point_opacity / coarse_is_background / coarse_mask /
-queried_shading / ray_mask).  Its forward is the fused MI355X path:
+queried_shading / ray_mask) over a ``NeuralPoints`` cloud (neural_points.py,
+re-exported here), whose opt.wcoord_query picks the querier.
+
+World grid (wcoord_query > 0, querier.py): the fused MI355X path
     pnr_query  (grid-resident march + layered KNN, device-side compaction)
  -> pnr_aggregate_fwd (gather + weights + PE + MFMA MLP + K-sum + colour MLP)
  -> pnr_composite_fwd (ray_dist + alpha composite + fill_invalid)
 with one small device->host read of the sample counts per ray batch (to size
-the feature buffer) and no ``raypos[R,400,3]`` / ``[R,SR,K,38]`` intermediates.
+the feature buffer) and no ``raypos[R,400,3]`` / ``[R,SR,K,38]`` intermediates
+(render_rays, render_rays_train; render_eval.py, render_train.py).
+
+Perspective frustum (wcoord_query 0, querier_p.py): the reference's forward as
+its seams (NeuralPoints.forward on pnr_pquery -> PointAggregator.forward ->
+ray_march.py), differentiable; or, for an evaluation frame, the same fused chain
+on pnr_pquery_build / pnr_pquery_bufs -> aggregate -> pnr_composite_fwd_p
+(render_pixels).
+
+``forward`` is inputs -> route -> frame -> assemble: one record of the call's
+inputs made scalar once (ForwardInputs), one place that picks among "train",
+"eval", "seams" and "pixels" (route), one record every route returns (Frame) and
+one function that makes the output dict of it (assemble).
 """
 from __future__ import annotations
 
-import numpy as np
+from dataclasses import dataclass
+from typing import Any
+
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from .aggregator import PointAggregator
-from .querier import COUNT_R_VALID, camera_tables, counts_dict, lighting_fast_querier, release_deferred
-from .querier_p import check_sizes, lighting_fast_querier as lighting_fast_querier_p
-from .render_eval import (EAGER, QUEUED, PixelBatch, RayBatch, RenderGraph, _PixelCall, _RenderCall,  # noqa: F401
-                          _RenderState, bg_channels)
+from .losses import _SparseConfLoss, _ZeroOneConfLoss
+from .neural_points import NeuralPoints
+from .querier import camera_tables
+from .querier_p import check_supported
+from .ray_march import fill_invalid, march_hit_rays, perspective_ray_dist
+from .render_eval import (EAGER, QUEUED, PixelBatch, RayBatch, RenderGraph, _CallQueue, _PixelCall,  # noqa: F401
+                          _RenderCall, _RenderState, bg_channels, query_params, with_h2_fallback)
 from .render_train import TRAIN_BYTES_PER_SAMPLE, _TrainAux, _TrainCall, march_aux  # noqa: F401
-
-
-class NeuralPoints(nn.Module):
-    """Point table of neural_points.NeuralPoints; opt.wcoord_query picks the
-    querier as neural_points.py:330 does: > 0 the world grid (querier.py), 0 the
-    perspective frustum (querier_p.py)."""
-
-    def __init__(self, opt, device, xyz=None, embedding=None, color=None, dirs=None, conf=None,
-                 Rw2c=None, emb_dtype=torch.float32):
-        """emb_dtype torch.bfloat16 stores points_embeding in bf16 (SURVEY config
-        c5: 104 B per point instead of 168; the bf16 render path reads it
-        directly, the fp32 paths from an fp32 copy; training needs fp32)."""
-        super().__init__()
-        if emb_dtype not in (torch.float32, torch.bfloat16):
-            raise L.PnrError(f"emb_dtype {emb_dtype}: float32 or bfloat16")
-        self.emb_dtype = emb_dtype
-        self._emb32 = (None, None)
-        self.opt = opt
-        self.device = torch.device(device)
-        self.xyz = nn.Parameter(torch.zeros((0, 3), device=self.device), requires_grad=False)
-        self.points_embeding = nn.Parameter(torch.zeros((1, 0, 32), device=self.device))
-        self.points_conf = None
-        self.points_dir = None
-        self.points_color = None
-        self.Rw2c = torch.eye(3, device=self.device)
-        if xyz is not None:
-            self.set_points(xyz, embedding, color, dirs, conf, Rw2c)
-        self.perspective = getattr(opt, "wcoord_query", 1) <= 0
-        self.querier = (lighting_fast_querier_p if self.perspective else lighting_fast_querier)(self.device, opt)
-
-    def set_points(self, xyz, embedding, color=None, dirs=None, conf=None, Rw2c=None):
-        """set_points (neural_points.py:480-546) with point_*_mode '1'; xyz is
-        trainable with --xyz_grad 1 (neural_points.py:270: the HIP backward's
-        pnr_aggregate_bwd_xyz, render_rays_train only)."""
-        dev = self.device
-        self.xyz = nn.Parameter(xyz.to(dev).float().reshape(-1, 3).contiguous(),
-                                requires_grad=getattr(self.opt, "xyz_grad", 0) > 0)
-        self.points_embeding = nn.Parameter(embedding.to(dev).to(self.emb_dtype).reshape(1, -1, 32).contiguous())
-        self.points_color = None if color is None else nn.Parameter(color.to(dev).float().reshape(1, -1, 3).contiguous())
-        self.points_dir = None if dirs is None else nn.Parameter(dirs.to(dev).float().reshape(1, -1, 3).contiguous())
-        self.points_conf = None if conf is None else nn.Parameter(conf.to(dev).float().reshape(1, -1, 1).contiguous())
-        # [3,3] uniform, or [N,3,3] per point (neural_points.py:289, 799; pnr_points.rw2c)
-        self.Rw2c = torch.eye(3, device=dev) if Rw2c is None else Rw2c.to(dev).float().contiguous()
-        if self.Rw2c.dim() == 3 and self.Rw2c.shape != (self.xyz.shape[0], 3, 3):
-            raise L.PnrError(f"per-point Rw2c must be [N,3,3], got {tuple(self.Rw2c.shape)}")
-
-    def embedding_fp32(self) -> torch.Tensor:
-        """points_embeding as fp32 [N,32] (the table itself, or a copy of the bf16
-        table cached on its storage and version)."""
-        e = self.points_embeding.detach().reshape(-1, 32)
-        if e.dtype == torch.float32:
-            return e.contiguous()
-        key = (e.data_ptr(), self.points_embeding._version, e.shape[0])
-        if self._emb32[0] != key:
-            self._emb32 = (key, e.float().contiguous())
-        return self._emb32[1]
-
-    def tables(self, campos=None, camrot=None, bf16: bool = False) -> tuple[L.Points, tuple]:
-        """pnr_points of the table; bf16 (the bf16 aggregate) passes a bf16
-        embedding table as emb_bf16 instead of an fp32 one."""
-        e = self.points_embeding.detach().reshape(-1, 32)
-        use_b = bf16 and e.dtype == torch.bfloat16
-        keep = (self.xyz.detach().contiguous(), None if use_b else self.embedding_fp32(),
-                None if self.points_color is None else self.points_color.detach().reshape(-1, 3).contiguous(),
-                None if self.points_dir is None else self.points_dir.detach().reshape(-1, 3).contiguous(),
-                None if self.points_conf is None else self.points_conf.detach().reshape(-1).contiguous(),
-                e.contiguous() if use_b else None)
-        p = L.Points(keep[0].shape[0], keep[0].data_ptr(), None, L.ptr(keep[1]), L.ptr(keep[2]), L.ptr(keep[3]),
-                     L.ptr(keep[4]), L.ptr(campos), L.ptr(camrot))
-        p.emb_bf16 = L.ptr(keep[5])
-        rw = self.rw2c_table()
-        p.rw2c = L.ptr(rw)
-        return p, keep + (rw,)
-
-    def rw2c_table(self):
-        """The per-point Rw2c as the kernels read it ([N,9] fp32), or None for a
-        uniform Rw2c (that one goes through the aggregator's pnr_mlp.rw2c)."""
-        rw = self.Rw2c
-        if rw is None or rw.dim() == 2:
-            return None
-        if rw.shape[0] != self.xyz.shape[0]:
-            raise L.PnrError(f"per-point Rw2c has {rw.shape[0]} rows, the cloud {self.xyz.shape[0]} points")
-        return rw.detach().reshape(-1, 9).float().contiguous()
-
-    def bytes_per_point(self) -> int:
-        """HBM bytes of one point's parameters (168 fp32, 104 with a bf16 embedding)."""
-        b = 12 + 32 * self.points_embeding.element_size()
-        for t, c in ((self.points_color, 3), (self.points_dir, 3), (self.points_conf, 1)):
-            if t is not None:
-                b += c * t.element_size()
-        return b
-
-    def w2pers(self, point_xyz, camrotc2w, campos):
-        """neural_points.py:687-693."""
-        point_xyz_shift = point_xyz[None, ...] - campos[:, None, :]
-        xyz = torch.sum(camrotc2w[:, None, :, :] * point_xyz_shift[:, :, :, None], dim=-2)
-        return torch.stack([xyz[:, :, 0] / xyz[:, :, 2], xyz[:, :, 1] / xyz[:, :, 2], xyz[:, :, 2]], dim=-1)
-
-    def forward(self, inputs):
-        """neural_points.py:782-812: query + gather, returns the 14-tuple the
-        reference PointAggregator consumes (API path; the fused renderer does
-        the gather inside pnr_aggregate_fwd instead)."""
-        camrotc2w, campos = inputs["camrotc2w"], inputs["campos"]
-        near, far = inputs["near"], inputs["far"]
-        pers = self.w2pers(self.xyz, camrotc2w, campos)
-        pixel_idx = inputs.get("pixel_idx")
-        if self.perspective:
-            for name in ("pixel_idx", "h", "w", "intrinsic"):
-                if inputs.get(name) is None:
-                    raise L.PnrError(f"NeuralPoints.forward with wcoord_query 0 (the perspective query) needs "
-                                     f"inputs[{name!r}]")
-            pixel_idx = pixel_idx.to(torch.int32)
-        (sample_pidx, sample_loc, sample_loc_w, sample_ray_dirs, ray_mask, vsize, ranges) = \
-            self.querier.query_points(pixel_idx, pers, self.xyz[None, ...], None,
-                                      inputs.get("h"), inputs.get("w"), inputs.get("intrinsic"),
-                                      torch.min(near).item(), torch.max(far).item(), inputs["raydir"],
-                                      campos, camrotc2w)
-        mask = sample_pidx >= 0
-        B, R, SR, K = sample_pidx.shape
-        idx = torch.clamp(sample_pidx, min=0).view(-1).long()
-        cat = torch.cat([self.xyz[None, ...], pers, self.points_embeding.float()], dim=-1)
-        g = torch.index_select(cat, 1, idx).view(B, R, SR, K, cat.shape[-1])
-
-        def sel(t, c):
-            return None if t is None else torch.index_select(t, 1, idx).view(B, R, SR, K, c)
-
-        rw = self.Rw2c if self.Rw2c.dim() == 2 else torch.index_select(self.Rw2c, 0, idx).view(B, R, SR, K, 3, 3)
-        return (sel(self.points_color, 3), rw, sel(self.points_dir, 3), sel(self.points_conf, 1),
-                g[..., 6:], g[..., 3:6], g[..., :3], mask, sample_loc, sample_loc_w, sample_ray_dirs,
-                ray_mask, vsize, 0)
 
 
 # The default is fp32h2, the measured headline path (fp32-accurate: the same
@@ -175,38 +60,41 @@ PROBE_KEYS = ("ray_max_shading_opacity", "ray_max_sample_loc_w", "ray_max_far_di
               "shading_avg_dir", "shading_avg_conf", "shading_avg_embedding")
 
 
-class _ZeroOneConfLoss(torch.autograd.Function):
-    """NeuralPointsRayMarching.zero_one_conf_loss on libpnr: the per-point entry
-    counts of the query's neighbour lists (pnr_point_counts), then one fused
-    reduction (pnr_zero_one_loss_fwd) and one backward kernel -- the same value
-    and gradient as torch's clamp / log / mean over the gathered [1, R'', SR, K]
-    conf_coefficient, in three launches and without host reads."""
+# the output dict of forward: key -> the Frame field it is a [1,R,...] view of
+FRAME_KEYS = (("coarse_raycolor", "color", (-1,)), ("coarse_point_opacity", "opacity", (-1,)),
+              ("coarse_is_background", "is_bg", (1,)), ("ray_mask", "ray_mask", ()))
+# neural_points_volumetric_model.py:335-338
+AUX_KEYS = ("weight", "blend_weight", "conf_coefficient")
 
-    @staticmethod
-    def forward(ctx, conf, bufs, SR, K, eps):
-        dev = conf.device
-        N = conf.numel()
-        c = conf.detach().float().contiguous()
-        counts = torch.zeros(N, dtype=torch.float32, device=dev)
-        L.check(L.lib().pnr_point_counts(L.ptr(bufs.pidx), L.ptr(bufs.counts), K, bufs.pidx.numel() // K,
-                                         L.ptr(counts), L.stream_ptr(dev)), "pnr_point_counts")
-        part = torch.empty(1024, dtype=torch.float32, device=dev)
-        out = torch.empty(3, dtype=torch.float32, device=dev)
-        L.check(L.lib().pnr_zero_one_loss_fwd(L.ptr(c), L.ptr(counts), N, L.c_void_p(bufs.count_ptr(COUNT_R_VALID)),
-                                              SR * K, eps, L.ptr(part), L.ptr(out), L.stream_ptr(dev)),
-                "pnr_zero_one_loss_fwd")
-        ctx.save_for_backward(c, counts, out)
-        ctx.eps = eps
-        return out[0].clone()
 
-    @staticmethod
-    def backward(ctx, g):
-        c, counts, out = ctx.saved_tensors
-        d = torch.empty_like(c)
-        g = g.reshape(1).float().contiguous()
-        L.check(L.lib().pnr_zero_one_loss_bwd(L.ptr(c), L.ptr(counts), c.numel(), ctx.eps, L.ptr(out), L.ptr(g),
-                                              L.ptr(d), L.stream_ptr(c.device)), "pnr_zero_one_loss_bwd")
-        return d, None, None, None, None
+@dataclass
+class ForwardInputs:
+    """One forward's inputs, every host number read once (the only .item() of near / far / h / w)."""
+    campos: Any
+    camrotc2w: Any
+    raydir: Any        # [R,3]
+    pixel_idx: Any
+    near: float
+    far: float
+    h: Any             # int, or None where nothing reads it (a world model without the 2-D renderer)
+    w: Any
+    intrinsic: Any
+    bg_color: Any      # None when bg_ray is passed
+    gt_image: Any
+    focal: Any = None
+
+
+@dataclass
+class Frame:
+    """What every route of forward returns: render_rays' four outputs ([R,..] or [1,R,..]), ray_valid
+    ([R]: queried_shading is one minus it), and the optional aux (AUX_KEYS) and probe (PROBE_KEYS) dicts."""
+    color: Any
+    opacity: Any
+    is_bg: Any
+    ray_mask: Any
+    ray_valid: Any
+    aux: Any = None
+    probe: Any = None
 
 
 class NeuralPointsRayMarching(nn.Module):
@@ -244,9 +132,7 @@ class NeuralPointsRayMarching(nn.Module):
         self.aggregator = aggregator if aggregator is not None else PointAggregator(opt).to(neural_points.device)
         self.chunk_rays = chunk_rays
         self._state = _RenderState()     # query buffers + aggregate scratch of the eager path
-        self._pending = []               # render_rays(sync=False) calls (_PendingCall) awaiting finish()
-        self._done = []                  # counts of calls a synchronous render completed, for the next finish()
-        self._sv_per_ray = None          # largest valid samples per ray seen (feature-buffer sizing)
+        self._queue = _CallQueue()       # render_rays(sync=False) calls awaiting finish(), and their sizing estimate
         self.overflow_rerenders = 0
         # fork's 2-D CNN after the composite (neural_points_volumetric_model.py:258-260, 343-344)
         self.neural_render_2d = None
@@ -258,7 +144,7 @@ class NeuralPointsRayMarching(nn.Module):
         self.last_train_aux = None    # _TrainAux of the last render_rays_train
         self._budget_dev = None       # a quarter of the device's memory, once asked for (render_train.train_budget)
         self._rw2c_key = None
-        self._pixel_ray_valid = None
+        self.path = self.path_why = None   # the route of the last forward and its reason (route)
         if getattr(opt, "which_render_func", "radiance") != "radiance" or \
                 getattr(opt, "which_blend_func", "alpha") != "alpha" or \
                 getattr(opt, "which_tonemap_func", "off") != "off":
@@ -326,33 +212,24 @@ class NeuralPointsRayMarching(nn.Module):
         chunk); if an activation left the f16 range, the call is rendered again
         on the fp32x3 path (bf16 split: same accuracy, fp32 range) and h2 stays
         off for these weights until they change (``h2_fallbacks`` counts it)."""
-        self._world_only("render_rays")
         self._sync_rw2c()
-        if self._pending and (sync or self._sv_per_ray is None):
-            # a synchronous call reads (and may clear) the shared range flag and the
-            # counts: complete the pending sync-free calls first so none of their
-            # checks is lost; their counts stay queued for the caller's next finish()
-            self._done = self.finish() + self._done
+        q = self._queue
+        if sync or q.sv_per_ray is None:
+            q.flush(self)   # a synchronous call reads (and may clear) the shared range flag and the counts
         batch = RayBatch(campos, camrot, raydir, near, far, bg_color, ray_cam)
         prec = self._precision_now()
         opts = dict(force_grid=force_grid, events=events)
-        if not sync and self._sv_per_ray is not None:
+        if not sync and q.sv_per_ray is not None:
             out, rec = self._render_rays(QUEUED, prec, batch, self._state, reuse_p1=reuse_p1, query_stream=query_stream,
-                                         capacity=self._sv_per_ray * 1.25, **opts)
-            self._pending.append(rec)
+                                         capacity=q.sv_per_ray * 1.25, **opts)
+            q.pending.append(rec)
             return out
-        n_ev = len(events) if events is not None else 0
-        out, _ = self._render_rays(EAGER, prec, batch, self._state, reuse_p1=reuse_p1, **opts)
-        if prec == "fp32h2" and not self.aggregator.h2_range_ok():
-            self._block_h2()
-            if events is not None:
-                del events[n_ev:]
-            out, _ = self._render_rays(EAGER, "fp32x3", batch, self._state, **opts)
-        return out
+        return with_h2_fallback(self, prec, events, lambda p, first: self._render_rays(
+            EAGER, p, batch, self._state, reuse_p1=reuse_p1 and first, **opts)[0])
 
     @torch.no_grad()
     def render_pixels(self, campos, camrotc2w, pixel_idx, h, w, intrinsic, near, far, bg_color, events=None,
-                      reuse_p1=False):
+                      reuse_p1=False, frame=False):
         """The fused evaluation frame of a perspective model (wcoord_query 0): pnr_pquery_build
         once, then per chunk of chunk_rays pixels pnr_pquery_bufs -> the precision's aggregate over the valid
         samples -> pnr_composite_fwd_p.  No gathered pair tensor, one host read (the counts) per chunk.
@@ -360,9 +237,11 @@ class NeuralPointsRayMarching(nn.Module):
         (ray_color [R,C], opacity [R,SR], is_bg [R], ray_mask [R] int8) and sets last_counts; ray_mask is the
         querier's (a hit ray without any neighbour keeps 1 and composites to the background).  One camera per
         call.  It never applies shpnt_jitter (the sample depths are the voxel centres).  events, reuse_p1 and
-        the fp32h2 fallback to fp32x3 as in render_rays; events also receives the ("build", ...) stage."""
-        np_, opt = self.neural_points, self.opt
-        if not np_.perspective:
+        the fp32h2 fallback to fp32x3 as in render_rays; events also receives the ("build", ...) stage.
+        frame=True (forward's fused route): the same as a Frame, whose ray_valid ([R] bool: the ray has a
+        valid sample) forward's queried_shading needs."""
+        opt = self.opt
+        if not self.neural_points.perspective:
             raise L.PnrError("render_pixels renders the perspective query (wcoord_query 0); this model queries the "
                              "world grid: call render_rays")
         if self.precision == "bf16":
@@ -370,44 +249,18 @@ class NeuralPointsRayMarching(nn.Module):
         if int(opt.K) > 8:
             raise L.PnrError(f"render_pixels: K = {int(opt.K)} neighbours per sample; the fused aggregate takes "
                              "1 .. 8")
-        if getattr(opt, "inverse", 0):
-            raise L.PnrError("--inverse 1 (disparity ray generation) is not supported")
-        if int(opt.NN) <= 0:
-            raise L.PnrError("NN == 0 (query_rand_along_ray: a reservoir seeded by time()) is not supported")
-        check_sizes(opt)
-        if self._pending:
-            self._done = self.finish() + self._done
+        check_supported(opt)
+        self._queue.flush(self)
         self._sync_rw2c()
-        dev = np_.xyz.device
-        h = int(h.reshape(-1)[0].item()) if torch.is_tensor(h) else int(h)
-        w = int(w.reshape(-1)[0].item()) if torch.is_tensor(w) else int(w)
-        intr = intrinsic.detach().cpu().numpy() if torch.is_tensor(intrinsic) else intrinsic
-        near = float(torch.min(near).item()) if torch.is_tensor(near) else float(near)
-        far = float(torch.max(far).item()) if torch.is_tensor(far) else float(far)
-        if pixel_idx is None:
-            ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.int32, device=dev),
-                                    torch.arange(w, dtype=torch.int32, device=dev), indexing="ij")
-            pix = torch.stack([xs, ys], -1).reshape(-1, 2).contiguous()
-        else:
-            pix = pixel_idx.to(dev).reshape(-1, 2).to(torch.int32).contiguous()
-        batch = PixelBatch(campos, camrotc2w, pix, h, w, np.asarray(intr, np.float32).reshape(-1, 3, 3)[0], near, far,
-                           bg_color)
-        prec = self._precision_now()
-        n_ev = len(events) if events is not None else 0
-        call = _PixelCall(self, prec, batch, self._state, events=events, reuse_p1=reuse_p1)
-        out, _ = call.run()
-        if prec == "fp32h2" and not self.aggregator.h2_range_ok():
-            self._block_h2()
-            if events is not None:
-                del events[n_ev:]
-            call = _PixelCall(self, "fp32x3", batch, self._state, events=events)
-            out, _ = call.run()
-        self._pixel_ray_valid = call.ray_valid   # [R] bool: the ray has a valid sample (forward's queried_shading)
-        return out
+        batch = PixelBatch.of(self.neural_points.xyz.device, campos, camrotc2w, pixel_idx, h, w, intrinsic, near, far,
+                              bg_color)
+        out = with_h2_fallback(self, self._precision_now(), events, lambda p, first: _PixelCall(
+            self, p, batch, self._state, events=events, reuse_p1=reuse_p1 and first).run()[0])
+        return Frame(*out) if frame else out[:4]
 
     def _render_rays(self, mode, precision, batch, state, **options):
         """One render call (render_eval._RenderCall and its modes) -> (outputs, its _PendingCall or None)."""
-        self._world_only("render_rays / RenderGraph")
+        self._world_only("render_rays / RenderGraph")   # the one door of every fused world render
         return _RenderCall(self, mode, precision, batch, state, **options).run()
 
     def render_camera(self, campos, camrotc2w, intrinsic, H, W, near, far, bg_color, dir_norm=False, **kw):
@@ -452,10 +305,6 @@ class NeuralPointsRayMarching(nn.Module):
         self._h2_blocked_key = self.aggregator.h2_key()
         self.h2_fallbacks += 1
 
-    def _observe(self, counts, rays):
-        r = counts["S_valid"] / max(rays, 1)
-        self._sv_per_ray = r if self._sv_per_ray is None else max(self._sv_per_ray, r)
-
     @torch.no_grad()
     def finish(self, upto=None):
         """Complete every ``render_rays(sync=False)`` call issued since the last
@@ -469,63 +318,12 @@ class NeuralPointsRayMarching(nn.Module):
         the later ones' counts are kept for the next finish()).  Returns the
         per-call sample counts (the ``last_counts`` dict of each call, in issue
         order)."""
-        if upto is None:   # freeing a collected GridHandle synchronises the device: not while later calls stay queued
-            release_deferred()
-        done = self._done
-        n_all = len(done) + len(self._pending)
-        k = n_all if upto is None else min(int(upto), n_all)
-        need = k - len(done)
-        if need > 0:
-            head = self._pending[:need]
-            head[-1].event.synchronize()
-            # the range flags as copied to pinned memory behind each call's event (a
-            # .item() here would queue behind -- and wait for -- the later calls)
-            if need < len(self._pending) and any(int(r.range_host[0]) != 0 for r in head if r.range_flag is not None):
-                head = self._pending
-                head[-1].event.synchronize()
-            self._pending = self._pending[len(head):]
-            done = done + self._complete(head)
-        self._done = done[k:]
-        return done[:k]
+        return self._queue.finish(self, upto)
 
-    def _complete(self, pend):
-        """finish()'s checks on calls whose last kernels have completed."""
-        # every fp32h2 call's own range flag (the packs, and their flag, are rebuilt when the weights change between
-        # calls), read from the call's pinned copy taken after its launches: the raised ones, by storage
-        h2 = [r for r in pend if r.range_flag is not None]
-        raised = {r.range_flag.data_ptr(): r.range_flag for r in h2 if int(r.range_host[0]) != 0}
-        if raised:
-            cur = self.aggregator.h2_key()
-            for f in raised.values():
-                f.zero_()
-            self.aggregator.h2_reset_range()
-            if any(r.h2_key == cur for r in h2):
-                self._h2_blocked_key = cur
-            self.h2_fallbacks += 1
-        counts = []
-        for rec in pend:
-            tot = dict(S_filled=0, S_valid=0, R_hit=0, R_valid=0, n_pairs=0, n_cand=0)
-            over = False
-            for (cap, rays), h in zip(rec.caps, rec.counts.tolist()):
-                c = counts_dict(h, n_used=False)
-                self._observe(c, rays)
-                over |= c["S_valid"] > cap
-                for k in tot:
-                    tot[k] += c[k]
-            rec_bad = rec.range_flag is not None and rec.range_flag.data_ptr() in raised
-            if over or rec_bad:
-                if rec.h2_key != self.aggregator.h2_key() or rec.grid_key != self.neural_points.querier.grid.key:
-                    raise L.PnrError("a render_rays(sync=False) call must be re-rendered, but the weights or the "
-                                     "points changed before finish(): call finish() before modifying the model")
-                out, _ = self._render_rays(EAGER, "fp32x3" if rec_bad else rec.precision, rec.batch, self._state,
-                                           force_grid=rec.force_grid)
-                for dst, src in zip(rec.out, out):
-                    dst.copy_(src)
-                tot = dict(self.last_counts)
-                self.overflow_rerenders += int(over)
-            counts.append(tot)
-        self.last_counts = counts[-1]
-        return counts
+    # the queue's state under the names it had on the module
+    _pending = property(lambda self: self._queue.pending)
+    _sv_per_ray = property(lambda self: self._queue.sv_per_ray,
+                           lambda self, v: setattr(self._queue, "sv_per_ray", v))
 
     @property
     def last_counts(self):
@@ -568,12 +366,10 @@ class NeuralPointsRayMarching(nn.Module):
         opacity.  conf_coefficient carries no graph here (no_grad render)."""
         self._world_only("eval_aux")
         np_ = self.neural_points
-        dev = raydir.device
         cp, cr = camera_tables(campos, camrot, None)
         xyz = np_.xyz.detach().contiguous()
-        bufs, hp, rays, qp = np_.querier.run(xyz, raydir.float().contiguous(), cp, cr, near, far, bufs=None)
-        cnt = bufs.read_counts()
-        return march_aux(self, rays, qp, bufs, raydir.shape[0], cnt["R_valid"], xyz, opacity)
+        bufs, _hp, rays, qp = np_.querier.run(xyz, raydir.float().contiguous(), cp, cr, near, far, bufs=None)
+        return march_aux(self, rays, qp, bufs, raydir.shape[0], bufs.read_counts()["R_valid"], xyz, opacity)
 
     @torch.no_grad()
     def probe_maps(self, campos, camrot, raydir, near, far, opacity):
@@ -605,7 +401,7 @@ class NeuralPointsRayMarching(nn.Module):
         bufs = None
         for c0 in range(0, R, chunk):
             c1 = min(c0 + chunk, R)
-            bufs, hp, rays, qp = np_.querier.run(xyz, raydir[c0:c1], cp, cr, near, far, bufs=bufs)
+            bufs, _hp, rays, qp = np_.querier.run(xyz, raydir[c0:c1], cp, cr, near, far, bufs=bufs)
             L.check(L.lib().pnr_probe(L.ctypes.byref(rays), L.ctypes.byref(qp), L.ctypes.byref(bufs.c),
                                       L.ctypes.byref(pts), L.ptr(op[c0:c1]),
                                       *(L.ptr(None if out[k] is None else out[k][0, c0:c1]) for k in PROBE_KEYS),
@@ -619,11 +415,16 @@ class NeuralPointsRayMarching(nn.Module):
         coarse_is_background [1,R,1], ray_mask [1,R] and the PROBE_KEYS maps."""
         raydir = raydir.reshape(-1, 3)
         color, opacity, is_bg, ray_mask = self.render_rays(campos, camrot, raydir, near, far, bg_color)
-        R = raydir.shape[0]
-        out = dict(coarse_raycolor=color.view(1, R, -1), coarse_point_opacity=opacity.view(1, R, -1),
-                   coarse_is_background=is_bg.view(1, R, 1), ray_mask=ray_mask.view(1, R))
-        out.update(self.probe_maps(campos, camrot, raydir, near, far, opacity))
-        return out
+        return self.assemble(Frame(color, opacity, is_bg, ray_mask, ray_mask,
+                                   probe=self.probe_maps(campos, camrot, raydir, near, far, opacity)))
+
+    def _last_train(self, who: str):
+        """(query buffers, their pnr_query_params) of the last training render, for the conf losses."""
+        bufs = self._train_conf_src
+        if bufs is None:
+            raise L.PnrError(f"{who}: no training render yet (call render_rays_train / forward in "
+                             "training mode first)")
+        return bufs, query_params(bufs.SR, bufs.K)
 
     def zero_one_conf_loss(self, zero_epsilon: float = 1e-3):
         """zero_one_loss(conf_coefficient) of the last render_rays_train, computed
@@ -635,10 +436,10 @@ class NeuralPointsRayMarching(nn.Module):
         query's own neighbour lists on the device (the R'' rays' filled samples
         hold every non-negative entry of sample_pidx; the other
         R'' * SR * K - sum_p count_p entries are empty slots, gathered as point 0):
-        no host read of R'' and no compaction."""
-        bufs = self._train_conf_src
+        no host read of R'' and no compaction (losses._ZeroOneConfLoss)."""
+        bufs, qp = self._last_train("zero_one_conf_loss")
         conf = self.neural_points.points_conf.reshape(-1)
-        return _ZeroOneConfLoss.apply(conf, bufs, self.opt.SR, self.opt.K, float(zero_epsilon))
+        return _ZeroOneConfLoss.apply(conf, bufs, qp.SR, qp.K, float(zero_epsilon))
 
     def sparse_conf_loss(self):
         """The sparse loss (base_rendering_model.py:652-662) of the last
@@ -652,13 +453,7 @@ class NeuralPointsRayMarching(nn.Module):
         compaction, no [1, R'', SR, K] tensors.  Without a conf table
         conf_coefficient is 1: a value without a gradient.  Bitwise repeatable
         (losses._SparseConfLoss)."""
-        from .losses import _SparseConfLoss
-        bufs = self._train_conf_src
-        if bufs is None:
-            raise L.PnrError("sparse_conf_loss: no training render yet (call render_rays_train / forward in "
-                             "training mode first)")
-        qp = L.QueryParams()
-        qp.SR, qp.K = bufs.SR, bufs.K
+        bufs, qp = self._last_train("sparse_conf_loss")
         np_ = self.neural_points
         return _SparseConfLoss.apply(np_.points_conf, np_.xyz.detach().contiguous(), bufs, qp)
 
@@ -669,93 +464,103 @@ class NeuralPointsRayMarching(nn.Module):
         v = torch.clamp(val, zero_epsilon, 1 - zero_epsilon)
         return torch.mean(torch.log(v) + torch.log(1 - v))
 
-    def _forward_perspective(self, campos, raydir, gt_image, bg_color, camrotc2w, pixel_idx, near, far, focal, h, w,
-                             intrinsic):
-        """forward with wcoord_query 0: the reference's forward as its seams
-        (neural_points_volumetric_model.py:288-341) -- NeuralPoints.forward's
-        14-tuple (pnr_pquery), PointAggregator.forward (the fused aggregate,
-        differentiable), ray_dist, ray_march, fill_invalid.  ray_mask is the
-        querier's (the column's far id > 0): a hit ray without any neighbour
-        keeps ray_mask 1 and composites to the background."""
-        from .ray_march import alpha_blend, radiance_render, ray_march
-        if getattr(self.opt, "prob", 0) == 1:
-            raise L.PnrError("opt.prob == 1 (the point-growing probe) is world-query only")
+    # ---------------------------------------------------------------- forward: inputs -> route -> frame -> assemble
+    def _inputs(self, campos, raydir, gt_image, bg_color, camrotc2w, pixel_idx, near, far, focal, h, w, intrinsic):
+        sized = self.neural_points.perspective or self.neural_render_2d is not None   # else nothing reads h, w
+
+        def size(v):
+            return L.host_scalar(v, int) if sized and v is not None else None
+
+        near, far = L.host_scalar(near, float, torch.min), L.host_scalar(far, float, torch.max)
+        return ForwardInputs(campos, camrotc2w, raydir.reshape(-1, 3), pixel_idx, near, far, size(h), size(w), intrinsic,
+                             bg_color, gt_image, focal)
+
+    def route(self, inputs: ForwardInputs):
+        """(route, why) of a forward, kept as path / path_why:
+        "train"  world model, a training step (model(...) then loss.backward(), as run/train_ft.py does: grad
+                 mode, train() and a parameter or bg_color to train): render_rays_train
+        "eval"   world model otherwise: render_rays (+ eval_aux, + probe_maps with opt.prob == 1)
+        "pixels" perspective model with fused_perspective, when render_pixels computes the same: no training
+                 step, no aux output wanted, no sample jitter to apply
+        "seams"  perspective model otherwise: the reference's forward as its seams, differentiable."""
+        opt = self.opt
+        train = torch.is_grad_enabled() and self.training and (
+            any(p.requires_grad for p in self.parameters())
+            or (torch.is_tensor(inputs.bg_color) and inputs.bg_color.requires_grad))
+        prob = getattr(opt, "prob", 0) == 1
+        if not self.neural_points.perspective:
+            if train and prob:
+                raise L.PnrError("opt.prob == 1 (the point-growing probe) is an evaluation render, as in the "
+                                 "reference's probe_hole: call the module in eval() mode or under no_grad")
+            r = ("train", "a training step") if train else ("eval", "no training step under way")
+        else:
+            if prob:
+                raise L.PnrError("opt.prob == 1 (the point-growing probe) is world-query only")
+            jitter = getattr(opt, "is_train", 0) != 0 and getattr(opt, "shpnt_jitter", "passfunc") != "passfunc"
+            declined = [why for cond, why in ((not self.fused_perspective, "fused_perspective is off"),
+                                              (train, "a training step"), (self.wants_aux(), "aux outputs wanted"),
+                                              (jitter, "a sample jitter, which render_pixels never applies")) if cond]
+            r = ("seams", declined[0]) if declined else ("pixels", "fused_perspective: an evaluation frame")
+        self.path, self.path_why = r
+        return r
+
+    def _frame_train(self, i: ForwardInputs) -> Frame:
+        color, opacity, is_bg, ray_mask = self.render_rays_train(i.campos, i.camrotc2w, i.raydir, i.near, i.far,
+                                                                 i.bg_color)
+        return Frame(color, opacity, is_bg, ray_mask, ray_mask, self.last_train_aux if self.wants_aux() else None)
+
+    def _frame_eval(self, i: ForwardInputs) -> Frame:
+        a = (i.campos, i.camrotc2w, i.raydir, i.near, i.far)
+        color, opacity, is_bg, ray_mask = self.render_rays(*a, i.bg_color)
+        aux = self.eval_aux(*a, opacity) if self.wants_aux() else None
+        # neural_points_volumetric_model_ori.py:351-372
+        probe = self.probe_maps(*a, opacity) if getattr(self.opt, "prob", 0) == 1 and color.shape[0] > 0 else None
+        return Frame(color, opacity, is_bg, ray_mask, ray_mask, aux, probe)
+
+    def _frame_pixels(self, i: ForwardInputs) -> Frame:
+        for name in ("pixel_idx", "h", "w", "intrinsic"):
+            if getattr(i, name) is None:
+                raise L.PnrError(f"forward with wcoord_query 0 (the perspective query) needs {name}")
+        return self.render_pixels(i.campos, i.camrotc2w, i.pixel_idx, i.h, i.w, i.intrinsic, i.near, i.far, i.bg_color,
+                                  frame=True)
+
+    def _frame_seams(self, i: ForwardInputs) -> Frame:
+        """The reference's forward as its seams (neural_points_volumetric_model.py:288-341):
+        NeuralPoints.forward's 14-tuple (pnr_pquery), PointAggregator.forward (the fused aggregate,
+        differentiable), then ray_march.py's ray_dist, march and fill_invalid.  ray_mask is the querier's (the
+        column's far id > 0): a hit ray without any neighbour keeps ray_mask 1 and composites to the background."""
         self._sync_rw2c()
         (s_color, s_rw2c, s_dir, s_conf, s_emb, s_pers, s_xyz, s_mask, s_loc, s_loc_w, s_dirs, ray_mask, vsize,
-         grid_vox_sz) = self.neural_points({"pixel_idx": pixel_idx, "camrotc2w": camrotc2w, "campos": campos,
-                                            "near": near, "far": far, "focal": focal, "h": h, "w": w,
-                                            "intrinsic": intrinsic, "gt_image": gt_image, "raydir": raydir})
+         grid_vox_sz) = self.neural_points({"pixel_idx": i.pixel_idx, "camrotc2w": i.camrotc2w, "campos": i.campos,
+                                            "near": i.near, "far": i.far, "focal": i.focal, "h": i.h, "w": i.w,
+                                            "intrinsic": i.intrinsic, "gt_image": i.gt_image, "raydir": i.raydir})
         feats, ray_valid, weight, conf = self.aggregator(s_color, s_rw2c, s_dir, s_conf, s_emb, s_pers, s_xyz, s_mask,
                                                          s_loc, s_loc_w, s_dirs, vsize, grid_vox_sz)
-        vz = float(vsize[2])   # the querier's (far - near) / z_depth_dim
-        rd = torch.cummax(s_loc[..., 2], dim=-1)[0]
-        rd = torch.cat([rd[..., 1:] - rd[..., :-1], torch.full(rd.shape[:2] + (1,), vz, device=rd.device)], dim=-1)
-        m = rd < 1e-8
-        if self.opt.raydist_mode_unit > 0:
-            m = torch.logical_or(m, rd > 2 * vz)
-        m = m.to(torch.float32)
-        rd = (rd * (1.0 - m) + m * vz) * ray_valid.float()
-        if rd.shape[1] == 0:   # no ray hit: nothing to march, fill_invalid writes every row
-            f32 = dict(dtype=torch.float32, device=rd.device)
-            color, opacity = torch.zeros((1, 0, feats.shape[-1] - 1), **f32), torch.zeros((1, 0, rd.shape[2]), **f32)
-            blend_weight, bg_T = torch.zeros((1, 0, rd.shape[2], 1), **f32), torch.zeros((1, 0, 1), **f32)
-        else:
-            color, _, opacity, _, blend_weight, bg_T, _ = ray_march(rd, ray_valid, feats, radiance_render, alpha_blend,
-                                                                    bg_color)
-        # fill_invalid (:354-389)
-        B, R = ray_mask.shape
-        dev = color.device
-        hit = ray_mask[0] > 0
-        C = color.shape[-1]
-        bg = torch.zeros(C, device=dev) if bg_color is None else bg_color.to(dev).float().reshape(-1)
-        full_color = (torch.ones((B, R, C), dtype=color.dtype, device=dev) * bg[None, None, :])
-        full_color[:, hit] = color
-        full_bg = torch.ones((B, R, 1), dtype=bg_T.dtype, device=dev)
-        full_bg[:, hit] = bg_T
-        full_op = torch.zeros((B, R, opacity.shape[2]), dtype=opacity.dtype, device=dev)
-        full_op[:, hit] = opacity
-        shading = torch.ones((B, R, 3), dtype=torch.float32, device=dev)
-        shading[:, hit] = torch.logical_not(torch.any(ray_valid, dim=-1, keepdim=True)).repeat(1, 1, 3).float()
-        out = dict(coarse_raycolor=full_color, coarse_point_opacity=full_op, coarse_is_background=full_bg,
-                   ray_mask=ray_mask, coarse_mask=1 - full_bg, queried_shading=shading)
-        if weight is not None:   # :335-338
-            out["weight"] = weight.detach()
-            out["blend_weight"] = blend_weight.detach()
-            out["conf_coefficient"] = conf
-        if self.neural_render_2d is not None:
-            img_h = int(h.item()) if torch.is_tensor(h) else int(h)
-            img_w = int(w.item()) if torch.is_tensor(w) else int(w)
-            out["final_coarse_raycolor"] = self.neural_render_2d(
-                out["coarse_raycolor"].reshape(1, img_h, img_w, -1)).reshape(1, -1, 3)
-        return out
+        # vsize[2]: the querier's (far - near) / z_depth_dim
+        rd = perspective_ray_dist(s_loc[..., 2], ray_valid, float(vsize[2]), self.opt.raydist_mode_unit)
+        color, opacity, blend_weight, bg_T = march_hit_rays(rd, ray_valid, feats, i.bg_color)
+        color, opacity, is_bg, any_valid = fill_invalid(ray_mask, color, opacity, bg_T, ray_valid, i.bg_color)
+        aux = None if weight is None else dict(weight=weight.detach(), blend_weight=blend_weight.detach(),
+                                               conf_coefficient=conf)
+        return Frame(color, opacity, is_bg, ray_mask, any_valid, aux)
 
-    def _fused_forward_applies(self, bg_color=None) -> bool:
-        """forward() may take render_pixels: no training step under way, no probe, no aux output wanted,
-        and no sample jitter to apply (render_pixels never jitters)."""
-        train = torch.is_grad_enabled() and self.training and (
-            any(p.requires_grad for p in self.parameters()) or (torch.is_tensor(bg_color) and bg_color.requires_grad))
-        opt = self.opt
-        jitter_free = getattr(opt, "is_train", 0) == 0 or getattr(opt, "shpnt_jitter", "passfunc") == "passfunc"
-        return not train and getattr(opt, "prob", 0) != 1 and not self.wants_aux() and jitter_free
-
-    def _forward_pixels(self, campos, bg_color, camrotc2w, pixel_idx, near, far, h, w, intrinsic):
-        """_forward_perspective's dict from render_pixels (fused_perspective)."""
-        for name, v in (("pixel_idx", pixel_idx), ("h", h), ("w", w), ("intrinsic", intrinsic)):
-            if v is None:
-                raise L.PnrError(f"forward with wcoord_query 0 (the perspective query) needs {name}")
-        color, opacity, is_bg, ray_mask = self.render_pixels(campos, camrotc2w, pixel_idx, h, w, intrinsic, near, far,
-                                                             bg_color)
-        R = color.shape[0]
-        shading = 1 - self._pixel_ray_valid.float().view(1, R, 1)   # 1 - (the ray has a valid sample)
-        out = dict(coarse_raycolor=color.view(1, R, -1), coarse_point_opacity=opacity.view(1, R, -1),
-                   coarse_is_background=is_bg.view(1, R, 1), ray_mask=ray_mask.view(1, R))
-        out["coarse_mask"] = 1 - out["coarse_is_background"]
-        out["queried_shading"] = shading.repeat(1, 1, 3)
-        if self.neural_render_2d is not None:
-            img_h = int(h.item()) if torch.is_tensor(h) else int(h)
-            img_w = int(w.item()) if torch.is_tensor(w) else int(w)
+    def assemble(self, frame: Frame, inputs: ForwardInputs | None = None) -> dict:
+        """The output dict of a Frame: FRAME_KEYS, then coarse_mask, queried_shading, the aux and probe
+        outputs and the 2-D renderer's final_coarse_raycolor.  Without inputs (probe_rays): FRAME_KEYS and
+        the probe maps only."""
+        R = frame.ray_mask.numel()
+        out = {key: getattr(frame, field).view(1, R, *tail) for key, field, tail in FRAME_KEYS}
+        if inputs is not None:
+            out["coarse_mask"] = 1 - out["coarse_is_background"]
+            out["queried_shading"] = (1 - frame.ray_valid.float().view(1, R, 1)).repeat(1, 1, 3)
+            if frame.aux is not None:
+                for k in AUX_KEYS:
+                    out[k] = frame.aux[k]
+        if frame.probe is not None:
+            out.update(frame.probe)
+        if inputs is not None and self.neural_render_2d is not None:
             out["final_coarse_raycolor"] = self.neural_render_2d(
-                out["coarse_raycolor"].reshape(1, img_h, img_w, -1)).reshape(1, -1, 3)
+                out["coarse_raycolor"].reshape(1, inputs.h, inputs.w, -1)).reshape(1, -1, 3)
         return out
 
     def forward(self, campos, raydir, gt_image=None, bg_color=None, camrotc2w=None, pixel_idx=None,
@@ -765,47 +570,9 @@ class NeuralPointsRayMarching(nn.Module):
         (NeuralRenderer, :343-344) adds final_coarse_raycolor (needs h, w)."""
         if raydir.dim() == 3 and raydir.shape[0] != 1:
             raise L.PnrError("batch size B > 1 is not supported (the reference uses B = 1)")
-        near_v = float(torch.min(near).item()) if torch.is_tensor(near) else float(near)
-        far_v = float(torch.max(far).item()) if torch.is_tensor(far) else float(far)
-        if "bg_ray" in kargs:
-            bg_color = None
-        if self.neural_points.perspective:
-            if self.fused_perspective and self._fused_forward_applies(bg_color):
-                return self._forward_pixels(campos, bg_color, camrotc2w, pixel_idx, near, far, h, w, intrinsic)
-            return self._forward_perspective(campos, raydir, gt_image, bg_color, camrotc2w, pixel_idx, near, far,
-                                             focal, h, w, intrinsic)
-        # training loop (model(...) then loss.backward(), as run/train_ft.py does):
-        # differentiable path; evaluation / no_grad: the fused forward
-        train = torch.is_grad_enabled() and self.training and (
-            any(p.requires_grad for p in self.parameters()) or (torch.is_tensor(bg_color) and bg_color.requires_grad))
-        prob = getattr(self.opt, "prob", 0) == 1
-        if train and prob:
-            raise L.PnrError("opt.prob == 1 (the point-growing probe) is an evaluation render, as in the "
-                             "reference's probe_hole: call the module in eval() mode or under no_grad")
-        if train:
-            color, opacity, is_bg, ray_mask = self.render_rays_train(campos, camrotc2w, raydir.reshape(-1, 3),
-                                                                     near_v, far_v, bg_color)
-            aux = self.last_train_aux if self.wants_aux() else None
-        else:
-            color, opacity, is_bg, ray_mask = self.render_rays(campos, camrotc2w, raydir.reshape(-1, 3),
-                                                               near_v, far_v, bg_color)
-            aux = self.eval_aux(campos, camrotc2w, raydir.reshape(-1, 3), near_v, far_v, opacity) \
-                if self.wants_aux() else None
-        R = color.shape[0]
-        mask_f = ray_mask.float().view(1, R, 1)
-        out = dict(coarse_raycolor=color.view(1, R, -1), coarse_point_opacity=opacity.view(1, R, -1),
-                   coarse_is_background=is_bg.view(1, R, 1), ray_mask=ray_mask.view(1, R))
-        out["coarse_mask"] = 1 - out["coarse_is_background"]
-        out["queried_shading"] = (1 - mask_f).repeat(1, 1, 3)
-        if aux is not None:   # neural_points_volumetric_model.py:335-338
-            out["weight"] = aux["weight"]
-            out["blend_weight"] = aux["blend_weight"]
-            out["conf_coefficient"] = aux["conf_coefficient"]
-        if prob and R > 0:   # neural_points_volumetric_model_ori.py:351-372
-            out.update(self.probe_maps(campos, camrotc2w, raydir.reshape(-1, 3), near_v, far_v, opacity))
-        if self.neural_render_2d is not None:
-            img_h = int(h.item()) if torch.is_tensor(h) else int(h)
-            img_w = int(w.item()) if torch.is_tensor(w) else int(w)
-            out["final_coarse_raycolor"] = self.neural_render_2d(
-                out["coarse_raycolor"].reshape(1, img_h, img_w, -1)).reshape(1, -1, 3)
-        return out
+        inputs = self._inputs(campos, raydir, gt_image, None if "bg_ray" in kargs else bg_color, camrotc2w, pixel_idx,
+                              near, far, focal, h, w, intrinsic)
+        name, _why = self.route(inputs)
+        frame = {"train": self._frame_train, "eval": self._frame_eval, "pixels": self._frame_pixels,
+                 "seams": self._frame_seams}[name](inputs)
+        return self.assemble(frame, inputs)

@@ -450,3 +450,36 @@ def test_render_pixels_refusals_and_events(cuda, scenes):
     torch.cuda.synchronize()
     assert [e[0] for e in events] == ["build"] + ["query", "aggregate", "composite"] * 2
     assert all(a.elapsed_time(b) >= 0 for _, a, b in events)
+
+
+def test_h2_range_flag_and_fallback_in_render_pixels(cuda, scenes):
+    """test_gpu_x3.py::test_h2_range_flag_and_fallback on render_pixels: an activation beyond the f16
+    range re-renders the call on fp32x3, bit-identical to an fp32x3 render_pixels; h2 stays off for those
+    weights until they change; a caller's events hold one call's stages."""
+    from pointnerf_amd.renderer import NeuralPointsRayMarching
+    sc, _ = scenes("C")
+    m = make_model(sc, cuda, formula_params(**PARAMS), "fp32h2")
+    agg = m.aggregator
+    mx = NeuralPointsRayMarching(sc["opt"], m.neural_points, agg, precision="fp32x3")
+    a = pixel_args(sc, inputs(sc, cuda))
+    one_call = ["build", "query", "aggregate", "composite"]
+    with torch.no_grad():
+        events = []
+        m.render_pixels(*a, events=events)
+        assert agg.h2_range_ok() and m.h2_fallbacks == 0 and [e[0] for e in events] == one_call
+        agg.block1[2].bias.fill_(1e6)            # block1.2 outputs ~1e6 > 65504 (repacked: new version)
+        events = [("mine", None, None)]
+        got = m.render_pixels(*a, events=events, reuse_p1=True)
+        assert m.h2_fallbacks == 1 and agg.h2_range_ok()   # flag consumed by the fallback
+        assert [e[0] for e in events] == ["mine"] + one_call   # the fp32x3 run's, the h2 run's dropped
+        want = mx.render_pixels(*a)
+        for x, y in zip(got, want):
+            assert torch.equal(x, y)
+        assert got[3].any()
+        again = m.render_pixels(*a)              # blocked weights: straight to fp32x3
+        assert m.h2_fallbacks == 1 and agg.h2_range_ok()
+        for x, y in zip(again, want):
+            assert torch.equal(x, y)
+        agg.block1[2].bias.fill_(0.0)            # new weights: h2 again, no trip
+        m.render_pixels(*a)
+        assert m.h2_fallbacks == 1 and m._h2_blocked_key is None and agg.h2_range_ok()

@@ -219,3 +219,20 @@ def test_fused_frame_paths_are_world_only(cuda, lone):
                  lambda: m.render_camera(a[0], a[1], float(sc["intrinsic"][0, 0]), sc["H"], sc["W"], 2.0, 6.0, a[5])):
         with pytest.raises(PnrError, match="world-query only"):
             call()
+
+
+@pytest.mark.parametrize("fused", [False, True])
+def test_module_forward_takes_float_near_far(cuda, fused):
+    """A perspective forward with Python-float near / far (and int h / w) equals the same call with
+    tensors, on the seam route and the fused one."""
+    sc = lone_point_scene(zero_one_loss_items=[])      # no aux output wanted: the fused route applies
+    m = model(sc, cuda, formula_params(salt=0.2))
+    m.fused_perspective = fused
+    inp = inputs(sc, cuda)
+    with torch.no_grad():
+        want = m(**inp)
+        assert m.path == ("pixels" if fused else "seams")
+        got = m(**dict(inp, near=2.0, far=6.0, h=sc["H"], w=sc["W"]))
+    assert set(got) == set(want) and want["ray_mask"].any()
+    for k in want:
+        assert torch.equal(got[k], want[k]), k
