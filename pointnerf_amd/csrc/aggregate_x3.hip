@@ -33,6 +33,8 @@
 // conflict-free ds_read_b128 and an accumulator quad one ds_write_b64 per
 // plane), next-tile PE planes [NPL][8][64][8], and double-buffered per-tile
 // extras / weights / point rows / sample flags.
+#include <cstdlib>
+
 #include "agg_common.h"
 
 
@@ -74,9 +76,13 @@ struct XL {
   static constexpr int OffH4 = OffWa + kHid * 4;           // h2: float [64][kP1Pitch] block3.2 accumulators
   static constexpr int OffTq = OffH4 + (H ? kXT * kP1Pitch * 4 : 0);   // int [4] tile of iteration i at i % 4
   static constexpr size_t Lds = (size_t)OffTq + 16;
+  // k_pairs_h2_rs only: launch constants, float [24] = Rw2c 0..8, campos 9..11,
+  // camrot 12..20, ba 21, int64 eff_n at 22 (see pairs_body)
+  static constexpr int OffCs = OffTq + 16;
+  static constexpr size_t LdsRS = (size_t)OffCs + 96;
   static_assert(OffSf % 16 == 0 && OffWa % 16 == 0 && OffH4 % 16 == 0, "16-B aligned LDS arrays");
   static_assert(kXT * kP1Pitch * 4 <= NPL * kPlaneX, "parked P1 fits the layer-input area");
-  static_assert(Lds <= 160 * 1024, "LDS budget");
+  static_assert(OffCs % 16 == 0 && LdsRS <= 160 * 1024, "LDS budget");
 };
 
 constexpr int kProducerPrio = 3;   // producer wave priority (s_setprio): measured 0: 110.6, 2: 110.1, 3: 109.6 ms
@@ -453,17 +459,37 @@ struct GatherState {
   int64_t row;
   int pid;
   float sw[3], sp[3];
+  float q3, q4;   // RS: sp[0] sp[2], sp[1] sp[2] (the subtrahends of d6[3], d6[4])
   int64_t dmap;
   bool active;
 };
 
-__device__ __forceinline__ void gather_row(const X3Args& A, int64_t tile, int lane, GatherState& g) {
+// Launch constants of the render specialisation (k_pairs_h2_rs): written once by
+// pairs_body, published by the P0 barrier, read by broadcast LDS reads in the
+// tile loop instead of global loads at a uniform address.
+template <bool RS>
+__device__ __forceinline__ int64_t tile_n(const X3Args& A, const char* lds) {
+  if constexpr (RS) return *reinterpret_cast<const int64_t*>(lds + XL<true>::OffCs + 88);
+  else return eff_n(A.s);
+}
+template <bool RS>
+__device__ __forceinline__ float alpha_bias(const X3Args& A, const char* lds) {
+  if constexpr (RS) return reinterpret_cast<const float*>(lds + XL<true>::OffCs)[21];
+  else return A.w.ba[0];
+}
+
+// LC: the sample count from the constants block (the loop of k_pairs_h2_rs; its
+// prologue runs before the block is published and reads *n_dev like the rest)
+template <bool LC = false>
+__device__ __forceinline__ void gather_row(const X3Args& A, int64_t tile, int lane, GatherState& g,
+                                           const char* lds = nullptr) {
   const int64_t v = tile * kXTS + (lane >> 3);
   g.tile = tile;
-  g.active = v < eff_n(A.s);
+  g.active = v < tile_n<LC>(A, lds);
   g.row = g.active ? sample_row(A.s, v) : 0;
 }
 
+template <bool RS = false>
 __device__ __forceinline__ void gather_sample(const X3Args& A, int lane, GatherState& g) {
   const int k = lane & 7, K = A.s.K;
   g.pid = (g.active && k < K) ? A.s.pidx[g.row * K + k] : -1;
@@ -473,17 +499,57 @@ __device__ __forceinline__ void gather_sample(const X3Args& A, int lane, GatherS
     g.sp[a] = g.active ? A.s.sample_p[g.row * 3 + a] : 0.f;
   }
   g.dmap = A.s.dir_map ? (int64_t)A.s.dir_map[g.row] : g.row;
+  if constexpr (RS) {
+    g.q3 = g.sp[0] * g.sp[2];
+    g.q4 = g.sp[1] * g.sp[2];
+  }
 }
 
-template <bool H, bool TR = false>
+// a0 b0 + a1 b1 + a2 b2 with the contraction written out: hipcc fuses
+// (x + y) + z of three products into two FMAs around either x or y, depending
+// on the code around it.  k_pairs_h2 compiles the gather's sums as below (the
+// same in its prologue and in its loop); k_pairs_h2_rs, with other code around
+// them, would fuse two of them the other way round and lose bit-identity, so it
+// states each one: sum012 = fma(a2, b2, fma(a1, b1, a0 b0)), sum102 = fma(a2, b2,
+// fma(a0, b0, a1 b1)).
+__device__ __forceinline__ float sum012(float a0, float b0, float a1, float b1, float a2, float b2) {
+  return __builtin_fmaf(a2, b2, __builtin_fmaf(a1, b1, a0 * b0));
+}
+__device__ __forceinline__ float sum102(float a0, float b0, float a1, float b1, float a2, float b2) {
+  return __builtin_fmaf(a2, b2, __builtin_fmaf(a0, b0, a1 * b1));
+}
+
+// RS (k_pairs_h2_rs): the launch-fixed options are constants (pairs_body) and
+// the sums of products are stated (sum012 / sum102); LC: its loop, where the
+// uniform Rw2c and the camera come from the LDS constants block.
+template <bool H, bool TR = false, bool RS = false, bool LC = false>
 __device__ __forceinline__ void gather(const X3Args& A, const GatherState& g, int nb, int nw, char* lds, int pw, int lane,
                                        float (&dr6)[6]) {
   using L = XL<H>;
   float Rw[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) Rw[i] = A.w.rw2c ? A.w.rw2c[i] : (i % 4 == 0 ? 1.f : 0.f);
   float cam_c[3] = {0.f, 0.f, 0.f}, cam_R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-  if (!A.pts.pers) {
+  if constexpr (LC) {   // the uniform Rw2c and the one camera: six broadcast ds_read_b128
+    const float4* c4 = reinterpret_cast<const float4*>(lds + L::OffCs);
+    float cs[24];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      const float4 v = c4[q];
+      cs[4 * q] = v.x;
+      cs[4 * q + 1] = v.y;
+      cs[4 * q + 2] = v.z;
+      cs[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Rw[i] = cs[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) cam_c[i] = cs[9 + i];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) cam_R[i] = cs[12 + i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Rw[i] = A.w.rw2c ? A.w.rw2c[i] : (i % 4 == 0 ? 1.f : 0.f);
+  }
+  if (!LC && !A.pts.pers) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) cam_c[i] = A.pts.campos[i];
 #pragma unroll
@@ -521,7 +587,15 @@ __device__ __forceinline__ void gather(const X3Args& A, const GatherState& g, in
         pdir[a] = A.pts.dir ? A.pts.dir[prow * 3 + a] : 0.f;
       }
     }
-    if (A.pts.pers) {
+    if constexpr (RS) {   // pair_pers' one-camera arm (world_to_pers)
+      const float s[3] = {pw3[0] - cam_c[0], pw3[1] - cam_c[1], pw3[2] - cam_c[2]};
+      float xc[3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) xc[j] = sum102(s[0], cam_R[j], s[1], cam_R[3 + j], s[2], cam_R[6 + j]);
+      pp[0] = __fdiv_rn(xc[0], xc[2]);
+      pp[1] = __fdiv_rn(xc[1], xc[2]);
+      pp[2] = xc[2];
+    } else if (A.pts.pers) {
 #pragma unroll
       for (int a = 0; a < 3; ++a) pp[a] = A.pts.pers[prow * 3 + a];
     } else {
@@ -533,29 +607,49 @@ __device__ __forceinline__ void gather(const X3Args& A, const GatherState& g, in
   d6[0] = pw3[0] - sw[0];
   d6[1] = pw3[1] - sw[1];
   d6[2] = pw3[2] - sw[2];
-  d6[3] = pp[0] * pp[2] - sp[0] * sp[2];
-  d6[4] = pp[1] * pp[2] - sp[1] * sp[2];
+  if constexpr (RS) {
+    d6[3] = __builtin_fmaf(pp[0], pp[2], -g.q3);
+    d6[4] = __builtin_fmaf(pp[1], pp[2], -g.q4);
+  } else {
+    d6[3] = pp[0] * pp[2] - sp[0] * sp[2];
+    d6[4] = pp[1] * pp[2] - sp[1] * sp[2];
+  }
   d6[5] = pp[2] - sp[2];
-  mat3(Rw, d6, dr6);
+  if constexpr (RS) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) dr6[j] = sum012(d6[0], Rw[3 * j], d6[1], Rw[3 * j + 1], d6[2], Rw[3 * j + 2]);
+  } else {
+    mat3(Rw, d6, dr6);
+  }
   dr6[3] = d6[3];
   dr6[4] = d6[4];
   dr6[5] = d6[5];
   if (A.pts.rw2c) rot_point(A.pts.rw2c, prow, d6, dr6);   // per-point Rw2c (agg_common.h)
   if (pw == 0) {
-    const float nrm = sqrtf(d6[0] * d6[0] + d6[1] * d6[1] + d6[2] * d6[2]);
+    const float nrm = RS ? sqrtf(sum012(d6[0], d6[0], d6[1], d6[1], d6[2], d6[2]))
+                         : sqrtf(d6[0] * d6[0] + d6[1] * d6[1] + d6[2] * d6[2]);
     const float wl = valid ? 1.f / fmaxf(nrm, 1e-6f) : 0.f;
     const float wsum = xor8_sum(wl);
     const float wn = wl / fmaxf(wsum, 1e-8f);
     const float confc = fminf(fmaxf(cf, 1e-4f), 1.f);
     const bool samp_valid = xor8_sum(valid ? 1.f : 0.f) > 0.f;
     float vrot[3], drot[3];
-    mat3(Rw, vd, vrot);
-    mat3(Rw, pdir, drot);
+    if constexpr (RS) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        vrot[j] = sum102(vd[0], Rw[3 * j], vd[1], Rw[3 * j + 1], vd[2], Rw[3 * j + 2]);
+        drot[j] = sum102(pdir[0], Rw[3 * j], pdir[1], Rw[3 * j + 1], pdir[2], Rw[3 * j + 2]);
+      }
+    } else {
+      mat3(Rw, vd, vrot);
+      mat3(Rw, pdir, drot);
+    }
     if (A.pts.rw2c) {
       rot_point(A.pts.rw2c, prow, pdir, drot);
       rot_point(A.pts.rw2c, active ? slot0_point(A.s, row) : 0, vd, vrot);
     }
-    const float dot = drot[0] * vrot[0] + drot[1] * vrot[1] + drot[2] * vrot[2];
+    const float dot = RS ? sum012(drot[0], vrot[0], drot[1], vrot[1], drot[2], vrot[2])
+                         : drot[0] * vrot[0] + drot[1] * vrot[1] + drot[2] * vrot[2];
     const float ex[8] = {col[0], col[1], col[2], drot[0] - vrot[0], drot[1] - vrot[1], drot[2] - vrot[2], dot, 1.f};
     float* exL = reinterpret_cast<float*>(lds + L::OffEx) + nb * 8 * kXT;
 #pragma unroll
@@ -898,10 +992,36 @@ __device__ __forceinline__ void consumer_loop(const X3Args& A, char* lds, int wi
 
 // Producer wave pw: P1 rows 16 pw .. 16 pw + 15 of a tile (1 KB each, one
 // coalesced float4 per lane per row) into registers.
+template <bool RS = false>
 __device__ __forceinline__ unsigned fetch_p1(f32x4n (&r)[16], const X3Args& A, const int* prow, int pw, int lane) {
-  // branch-free: every lane loads (row 0 for an empty slot) and zeroes afterwards,
-  // so the 16 loads issue back to back; streamed once -> non-temporal (keeps the
-  // weight packs in L2)
+  // every lane loads (row 0 for an empty slot) and zeroes afterwards; streamed
+  // once -> non-temporal (keeps the weight packs in L2)
+  if constexpr (RS) {
+    // no used_map (resolved at launch): the 16 row ids, contiguous in LDS and the
+    // same for every lane, come as four ds_read_b128 behind one wait and move to
+    // scalar registers; an empty slot is a select, so the 16 row loads (scalar
+    // row base + lane offset) issue back to back without a branch
+    const int4* p4 = reinterpret_cast<const int4*>(prow + 16 * pw);
+    int pr[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int4 v = p4[q];
+      pr[4 * q] = v.x;
+      pr[4 * q + 1] = v.y;
+      pr[4 * q + 2] = v.z;
+      pr[4 * q + 3] = v.w;
+    }
+    unsigned empty = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = __builtin_amdgcn_readfirstlane(pr[i]);
+      r[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4n*>(A.p1 + (int64_t)(row < 0 ? 0 : row) * kHid) +
+                                        lane);
+      empty |= (row < 0 ? 1u : 0u) << i;
+    }
+    return empty;
+  }
+  // (general kernels: a per-row branch on the empty slot and on used_map)
   int64_t rows[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
@@ -943,11 +1063,11 @@ struct TailState {
 
 // PART 0: pairs k = 0..3 of every sample; PART 1: k = 4..7, the reductions and
 // the stores (the halves run in two producer segments, see producer_loop)
-template <int PART, bool TR = false>
+template <int PART, bool TR = false, bool RS = false>
 __device__ __forceinline__ void producer_tail(const X3Args& A, char* lds, int slot, int64_t tile, int pw, int lane,
                                               TailState& ts, float& chk) {
   using L = XL<true>;
-  const int64_t n = eff_n(A.s);
+  const int64_t n = tile_n<RS>(A, lds);
   const int j = 2 * pw + (lane >> 5), ng = lane & 31;
   const float* H4 = reinterpret_cast<const float*>(lds + L::OffH4);
   const float* wtL = reinterpret_cast<const float*>(lds + L::OffWt) + slot * kXT + 8 * j;
@@ -985,7 +1105,7 @@ __device__ __forceinline__ void producer_tail(const X3Args& A, char* lds, int sl
   float r1 = (b2 ? r2[1] : r2[0]) + __shfl_xor(b2 ? r2[0] : r2[1], 4);
   r1 += __shfl_xor(r1, 2);
   r1 += __shfl_xor(r1, 1);
-  const float pk = r1 + A.w.ba[0];
+  const float pk = r1 + alpha_bias<RS>(A, lds);
   if (TR && (ng & 3) == 0 && tile * kXTS + j < n) A.sv.pa[tile * kXT + 8 * j + (ng >> 2)] = pk;
   const float alpha_k = A.w.act_super ? softplus(pk - 1.f) : fmaxf(pk, 0.f);
   float as = wtL[ng >> 2] * alpha_k;   // each k held by 4 lanes: sum over bits 2..4
@@ -1019,7 +1139,7 @@ __device__ __forceinline__ void producer_tail(const X3Args& A, char* lds, int sl
   }
 }
 
-template <bool H, bool TR = false>
+template <bool H, bool TR = false, bool RS = false>
 __device__ __forceinline__ void producer_loop(const X3Args& A, char* lds, int pw, int lane) {
   using L = XL<H>;
   // h2 inference only: producer work moved into an activation-store window (the
@@ -1033,14 +1153,14 @@ __device__ __forceinline__ void producer_loop(const X3Args& A, char* lds, int pw
   float dr6[6];
   GatherState g;
   gather_row(A, first_tile(ntiles), lane, g);
-  gather_sample(A, lane, g);
-  gather<H, TR>(A, g, 0, 0, lds, pw, lane, dr6);
+  gather_sample<RS>(A, lane, g);
+  gather<H, TR, RS>(A, g, 0, 0, lds, pw, lane, dr6);
   pe_planes<H, 0, TR>(lds, pw, lane, dr6, &A, &g);
   pe_planes<H, 1, TR>(lds, pw, lane, dr6, &A, &g);
   int* TQ = reinterpret_cast<int*>(lds + L::OffTq);
   if (pw == 0 && lane == 0) TQ[1] = (int)take_tile(A, ntiles);
   X3_SYNC();   // P0: prow of the first tile visible to all producers, TQ[1] too
-  p1e = fetch_p1(p1r, A, reinterpret_cast<const int*>(lds + L::OffPr), pw, lane);
+  p1e = fetch_p1<RS>(p1r, A, reinterpret_cast<const int*>(lds + L::OffPr), pw, lane);
   X3_SYNC();   // S0
   float chk = 0.f;   // h2 tails: 0 * outputs (producer_tail)
   TailState ts;
@@ -1054,27 +1174,27 @@ __device__ __forceinline__ void producer_loop(const X3Args& A, char* lds, int pw
     // a tile taken by a workgroup that stops would be lost)
     if (pw == 0 && lane == 0) TQ[(it + 2) & 3] = next < ntiles ? (int)take_tile(A, ntiles) : (int)ntiles;
     park_p1(p1r, p1e, lds, pw, lane);   // the layer-input planes are free since the last S7
-    gather_row(A, next, lane, g);
+    gather_row<RS>(A, next, lane, g, lds);
     X3_SYNC();   // S1
     // alpha of the previous tile (its partials stay until this tile's K sums, after S6)
     if (!H && pw == 0 && it > 0) finalize_alpha<H, TR>(A, lds, nbuf, prev, lane);
     X3_SYNC();   // S1b
-    gather_sample(A, lane, g);
+    gather_sample<RS>(A, lane, g);
     X3_SYNC();   // S2
     // during block1.2: gather of the next tile (its slots are free: their last
     // readers were the previous finalize / tail)
-    gather<H, TR>(A, g, nbuf, nw, lds, pw, lane, dr6);
+    gather<H, TR, RS, RS>(A, g, nbuf, nw, lds, pw, lane, dr6);
     if constexpr (H)   // first half of the previous tile's tail
-      if (it > 0) producer_tail<0, TR>(A, lds, (it + 2) % 3, prev, pw, lane, ts, chk);
+      if (it > 0) producer_tail<0, TR, RS>(A, lds, (it + 2) % 3, prev, pw, lane, ts, chk);
     X3_SYNC();   // S3: the next tile's point rows are in LDS
     // the P1 rows travel during block3.0 / block3.2 (loads stay in flight across the barriers)
-    p1e = fetch_p1(p1r, A, reinterpret_cast<const int*>(lds + L::OffPr) + nbuf * kXT, pw, lane);
+    p1e = fetch_p1<RS>(p1r, A, reinterpret_cast<const int*>(lds + L::OffPr) + nbuf * kXT, pw, lane);
     X3_SYNC();   // S4
     if constexpr (!SW) pe_planes<H, 0, TR>(lds, pw, lane, dr6, &A, &g);   // during block3.0 (PE planes free since S1)
     // (h2) during block3.0: the second half of the previous tile's tail (its
     // accumulators are overwritten after this tile's S6)
     if constexpr (H)
-      if (it > 0) producer_tail<1, TR>(A, lds, (it + 2) % 3, prev, pw, lane, ts, chk);
+      if (it > 0) producer_tail<1, TR, RS>(A, lds, (it + 2) % 3, prev, pw, lane, ts, chk);
     X3_SYNC();   // S5
     // SW: PE part 1 beside the consumers' act3 store, which leaves half of the
     // SIMD's issue slots unused, instead of beside block3.0's MFMA stream (the
@@ -1091,8 +1211,8 @@ __device__ __forceinline__ void producer_loop(const X3Args& A, char* lds, int pw
   if constexpr (H) {
     // the last tile's tail (its accumulators were parked before the final S7)
     if (it > 0) {
-      producer_tail<0, TR>(A, lds, (it - 1) % 3, prev, pw, lane, ts, chk);
-      producer_tail<1, TR>(A, lds, (it - 1) % 3, prev, pw, lane, ts, chk);
+      producer_tail<0, TR, RS>(A, lds, (it - 1) % 3, prev, pw, lane, ts, chk);
+      producer_tail<1, TR, RS>(A, lds, (it - 1) % 3, prev, pw, lane, ts, chk);
     }
     if (A.wx.range_flag && chk != 0.f) atomicOr(A.wx.range_flag, 1);
   } else {
@@ -1100,22 +1220,57 @@ __device__ __forceinline__ void producer_loop(const X3Args& A, char* lds, int pw
   }
 }
 
-template <bool H, bool TR = false>
+template <bool H, bool TR = false, bool RS = false>
 __device__ __forceinline__ void pairs_body(const X3Args& A) {
+  static_assert(!RS || (H && !TR), "render specialisation: the h2 inference kernel only");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   // alpha_branch.0 weights for the consumers' tail
   if (threadIdx.x < kHid) reinterpret_cast<float*>(lds + XL<H>::OffWa)[threadIdx.x] = A.w.wa[threadIdx.x];
+  if constexpr (RS) {   // launch constants (XL::OffCs), visible to the producers' loop after P0
+    if (wid == 4) {
+      float* cs = reinterpret_cast<float*>(lds + XL<H>::OffCs);
+      if (lane < 9) cs[lane] = A.w.rw2c ? A.w.rw2c[lane] : (lane % 4 == 0 ? 1.f : 0.f);
+      else if (lane < 12) cs[lane] = A.pts.campos[lane - 9];
+      else if (lane < 21) cs[lane] = A.pts.camrot[lane - 12];
+      else if (lane == 21) cs[21] = A.w.ba[0];
+      else if (lane == 22) *reinterpret_cast<int64_t*>(cs + 22) = eff_n(A.s);
+    }
+  }
   if (wid < 4) {
     X3_SYNC();   // P0
     consumer_loop<H, TR>(A, lds, wid, lane);
   } else {
-    producer_loop<H, TR>(A, lds, wid - 4, lane);
+    producer_loop<H, TR, RS>(A, lds, wid - 4, lane);
   }
+}
+
+// What launch_pairs_split checks on the host before it picks k_pairs_h2_rs: the
+// frame render's options (render_eval.py aggregate_chunk).
+inline bool render_route(const X3Args& a) {
+  return !a.pts.pers && !a.pts.used_map && !a.pts.rw2c && a.pts.color && a.pts.dir && a.pts.conf &&
+         a.s.dir_map && !a.s.ray_cam && !a.out_weight && !a.out_conf;
 }
 
 __global__ void __launch_bounds__(512, 1) k_pairs_x3(X3Args A) { pairs_body<false>(A); }
 __global__ void __launch_bounds__(512, 1) k_pairs_h2(X3Args A) { pairs_body<true>(A); }
+// k_pairs_h2 for launches with render_route(): the options fixed for the launch
+// are constants here (no per-tile branch on them, no register for the absent
+// tables), the uniform Rw2c, the camera, ba and the sample count come from the
+// LDS constants block, and fetch_p1 reads its row ids wide.  Same arithmetic:
+// bit-identical outputs (tests/test_gpu_h2_producers.py).
+__global__ void __launch_bounds__(512, 1) k_pairs_h2_rs(X3Args A0) {
+  X3Args A = A0;
+  A.pts.pers = nullptr;
+  A.pts.used_map = nullptr;
+  A.pts.rw2c = nullptr;
+  A.s.ray_cam = nullptr;
+  A.out_weight = nullptr;
+  A.out_conf = nullptr;
+  __builtin_assume(A.pts.color != nullptr && A.pts.dir != nullptr && A.pts.conf != nullptr);
+  __builtin_assume(A.s.dir_map != nullptr);
+  pairs_body<true, false, true>(A);
+}
 // training forward (pnr_aggregate_fwd_train_x3): k_pairs_x3 + the saves of k_pairs<true>
 __global__ void __launch_bounds__(512, 1) k_pairs_x3_train(X3Args A) { pairs_body<false, true>(A); }
 // training forward on fp32h2 (pnr_aggregate_fwd_train_h2): k_pairs_h2 + the same saves, hid in fp32 rows
@@ -1553,6 +1708,9 @@ int launch_pairs_split(const pnr_points& pts, const pnr_samples& s, const pnr_ml
   static bool attr[2] = {false, false};   // (per H instantiation)
   if (!attr[sv ? 1 : 0]) {
     PNR_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)XL<H>::Lds));
+    if (H && !sv)
+      PNR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pairs_h2_rs),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)XL<true>::LdsRS));
     attr[sv ? 1 : 0] = true;
   }
   X3Args a;
@@ -1573,6 +1731,8 @@ int launch_pairs_split(const pnr_points& pts, const pnr_samples& s, const pnr_ml
   const int64_t tiles = cdiv(s.n_max, kXTS);
   if (H && sv)
     hipLaunchKernelGGL(k_pairs_h2_train, dim3(grid_for(tiles, 1, 256)), dim3(512), XL<H>::Lds, st, a);
+  else if (H && render_route(a) && !getenv("PNR_H2_GENERAL"))   // (the variable: A/B and route tests)
+    hipLaunchKernelGGL(k_pairs_h2_rs, dim3(grid_for(tiles, 1, 256)), dim3(512), XL<true>::LdsRS, st, a);
   else if (H)
     hipLaunchKernelGGL(k_pairs_h2, dim3(grid_for(tiles, 1, 256)), dim3(512), XL<H>::Lds, st, a);
   else if (sv)
