@@ -1192,7 +1192,7 @@ extern "C" int pnr_neural_render_fwd_h2(const float* x, int32_t H, int32_t W, co
   a.Cin = 64;
   a.in_max = words + 1 * kWS;
   a.wp = static_cast<const uint4*>(w->wp1);
-  a.wscale = w->ws + 4;
+  a.wscale = w->ws + 2;
   a.bias = w->b1;
   a.cout = 32;
   a.out = net1;
@@ -1281,7 +1281,7 @@ extern "C" int pnr_neural_render_bwd_h2(const float* x, const float* fwd_scratch
   a.in_max = words + 1 * kWS;
   a.cin_real = 32 + 3;
   a.wp = static_cast<const uint4*>(wt->wt1);
-  a.wscale = wt->ws + 4;
+  a.wscale = wt->ws + 2;
   a.cout = 64;
   a.ldo = 96;
   a.out = cat0;
