@@ -79,7 +79,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 30
+#define PNR_ABI_VERSION 31
 
 enum {
   PNR_OK = 0,
@@ -276,6 +276,12 @@ typedef struct {
   const float* rw2c;                   /* [3,3] uniform Rw2c (identity default) */
   float neg_slope;                     /* LeakyReLU slope (0 = ReLU)           */
   int32_t act_super;                   /* 1: softplus(x-1), 0: relu(x)         */
+  int32_t intrp_order;                 /* agg_intrp_order (ABI 31): 0 or 2 = order 2 (alpha per
+                                          pair, K-summed); 1 = order 1 (alpha from the K-summed
+                                          block3 features, raw2out_color on the colour branch:
+                                          point_aggregators.py:573-599).  1 is taken by
+                                          pnr_aggregate_fwd, _x3, _h2 and _masked only; every
+                                          other call with a pnr_mlp returns PNR_EINVAL        */
 } pnr_mlp;
 
 typedef struct {
@@ -315,6 +321,14 @@ typedef struct {
                            the kernels then take min(n_used, *n_used_dev) rows, n_used
                            being the capacity -- a training forward that never reads
                            the count on the host (ABI 19)                               */
+  int32_t emb_dim;      /* E (ABI 31): floats per row of emb, tightly packed [N, E], 1..64;
+                           0 = 32.  w1af is then the pack of block1.0[:, :7E] + bias
+                           (input rows: emb 0..E-1, PE row E + 6c + {s0,c0,s1,c1,s2,c2} of
+                           channel c) and w1bf of block1.0[:, 7E:7E+60].  E != 32 is
+                           taken by pnr_aggregate_fwd, _x3, _h2, _masked and
+                           pnr_point_pre_h2 only (emb then needs 4-B alignment when
+                           E % 4 != 0); every other call with a pnr_points returns
+                           PNR_EINVAL                                                   */
 } pnr_points;
 
 typedef struct {

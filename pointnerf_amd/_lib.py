@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PNR_LIB", os.path.join(_HERE, "libpnr.so"))
 c_int, c_int8, c_int32, c_int64 = ctypes.c_int, ctypes.c_int8, ctypes.c_int32, ctypes.c_int64
 c_float, c_size_t, c_void_p = ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 PNR_OK, PNR_EINVAL, PNR_EOVERFLOW, PNR_EHIP, PNR_ENOMEM = 0, 1, 2, 3, 4
-ABI_VERSION = 30
+ABI_VERSION = 31
 SEED_CAM_TILE = 64   # PNR_SEED_CAM_TILE (include/pnr.h)
 FEAT_H_PITCH = 136   # PNR_FEAT_H_PITCH: uint16 per bf16 feature row (pnr_aggregate_fwd_bf16_hf)
 HEAD_BWD_BLOCKS = 512   # PNR_HEAD_BWD_BLOCKS (include/pnr.h)
@@ -71,7 +71,8 @@ class Mlp(ctypes.Structure):
                 ("w3f", c_void_p), ("b3", c_void_p), ("w4f", c_void_p), ("b4", c_void_p),
                 ("wa", c_void_p), ("ba", c_void_p), ("wc1f", c_void_p), ("bc1", c_void_p),
                 ("wc2f", c_void_p), ("bc2", c_void_p), ("wc3f", c_void_p), ("bc3", c_void_p),
-                ("rw2c", c_void_p), ("neg_slope", c_float), ("act_super", c_int32)]
+                ("rw2c", c_void_p), ("neg_slope", c_float), ("act_super", c_int32),
+                ("intrp_order", c_int32)]   # 0 / 2: order 2, 1: order 1 (ABI 31)
 
 
 class NeuralRenderW(ctypes.Structure):
@@ -103,7 +104,7 @@ class Points(ctypes.Structure):
                 ("dir", c_void_p), ("conf", c_void_p), ("campos", c_void_p), ("camrot", c_void_p),
                 ("used", c_void_p), ("n_used", c_int64), ("used_map", c_void_p),
                 ("p1_ready", c_int32), ("emb_bf16", c_void_p), ("rw2c", c_void_p),
-                ("n_used_dev", c_void_p)]
+                ("n_used_dev", c_void_p), ("emb_dim", c_int32)]   # emb_dim: 0 = 32 (ABI 31)
 
 
 class Samples(ctypes.Structure):

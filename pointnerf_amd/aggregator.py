@@ -2,7 +2,9 @@
 
 Same module tree and ``state_dict`` names as
 models/aggregators/point_aggregators.py:12-348 for the lego configuration
-(viewmlp, agg_intrp_order 2, linear kernel, agg_dist_pers 20): ``block1.{0,2}``,
+(viewmlp, agg_intrp_order 2, linear kernel, agg_dist_pers 20) and for the DTU
+scripts' aggregator flags (point_features_dim up to 64, agg_intrp_order 1 or 2;
+evaluation only): ``block1.{0,2}``,
 ``block3.{0,2}``, ``alpha_branch.0``, ``color_branch.{0,2,4}``, so reference
 checkpoints load with ``load_state_dict(strict=False)`` as in
 mvs_points_volumetric_model.py:320-335.  ``forward`` keeps the 13-argument
@@ -19,8 +21,8 @@ import torch.nn as nn
 
 from . import _lib as L
 
-SUPPORTED = dict(which_agg_model="viewmlp", agg_intrp_order=2, agg_distance_kernel="linear",
-                 agg_dist_pers=20, point_features_dim=32, num_feat_freqs=3, dist_xyz_freq=5,
+SUPPORTED = dict(which_agg_model="viewmlp", agg_distance_kernel="linear",
+                 agg_dist_pers=20, num_feat_freqs=3, dist_xyz_freq=5,
                  num_viewdir_freqs=4, shading_feature_num=256, shading_feature_mlp_layer1=2,
                  shading_feature_mlp_layer2=0, shading_feature_mlp_layer3=2,
                  shading_alpha_mlp_layer=1, shading_color_mlp_layer=4,
@@ -28,12 +30,21 @@ SUPPORTED = dict(which_agg_model="viewmlp", agg_intrp_order=2, agg_distance_kern
 # C_out: 128 = the fork (colour head cut, point_aggregators.py:343, 637-638);
 # 3 = upstream (Linear(128, 3) + raw2out_color restored, rgb_head.hip)
 COLOR_CHANNELS = (128, 3)
+EMB_DIMS = range(1, 65)     # point_features_dim (pnr_points.emb_dim); 32 = lego, 63 = the DTU scripts
+INTRP_ORDERS = (1, 2)       # agg_intrp_order (pnr_mlp.intrp_order); 1 = the dtu_test_inf scripts
 
 
 def check_supported(opt):
     bad = {k: (getattr(opt, k, v), v) for k, v in SUPPORTED.items() if getattr(opt, k, v) != v}
     if getattr(opt, "shading_color_channel_num", 128) not in COLOR_CHANNELS:
         bad["shading_color_channel_num"] = (opt.shading_color_channel_num, COLOR_CHANNELS)
+    if getattr(opt, "point_features_dim", 32) not in EMB_DIMS:
+        bad["point_features_dim"] = (opt.point_features_dim, "1..64")
+    order = getattr(opt, "agg_intrp_order", 2)
+    if order not in INTRP_ORDERS:
+        bad["agg_intrp_order"] = (order, INTRP_ORDERS)
+    elif order == 1 and getattr(opt, "shading_color_channel_num", 128) != 128:
+        bad["agg_intrp_order"] = (1, "2 with shading_color_channel_num 3")
     if getattr(opt, "dist_xyz_deno", 0.0) != 0.0:
         bad["dist_xyz_deno"] = (opt.dist_xyz_deno, 0.0)
     for k in ("agg_feat_xyz_mode", "agg_alpha_xyz_mode", "agg_color_xyz_mode"):
@@ -41,6 +52,18 @@ def check_supported(opt):
             bad[k] = (getattr(opt, k), "None")
     if bad:
         raise L.PnrError(f"aggregator configuration not implemented by libpnr: {bad}")
+
+
+def require_default_dims(opt, who: str):
+    """Training, the bf16 path and the point-growing probe know point_features_dim 32 and
+    agg_intrp_order 2 only: raised from the host layer, before any launch."""
+    e, order = int(getattr(opt, "point_features_dim", 32)), int(getattr(opt, "agg_intrp_order", 2))
+    if e != 32:
+        raise L.PnrError(f"{who}: point_features_dim {e} is evaluation only (fp32, fp32x3, fp32h2); "
+                         "this path needs point_features_dim 32")
+    if order != 2:
+        raise L.PnrError(f"{who}: agg_intrp_order {order} is evaluation only (fp32, fp32x3, fp32h2); "
+                         "this path needs agg_intrp_order 2")
 
 
 def _xavier_(lin: nn.Linear, gain: float):
@@ -270,7 +293,7 @@ def frag_unpack(F: torch.Tensor, kin: int, out_f: int = 256) -> torch.Tensor:
 
 
 class PointAggregator(nn.Module):
-    """point_aggregators.PointAggregator (viewmlp, order 2) on libpnr.so."""
+    """point_aggregators.PointAggregator (viewmlp, order 1 or 2) on libpnr.so."""
 
     def __init__(self, opt):
         super().__init__()
@@ -284,8 +307,12 @@ class PointAggregator(nn.Module):
         else:
             raise L.PnrError(f"act_type {act} not implemented by libpnr")
         self.act_super = int(getattr(opt, "act_super", 1))
-        # shapes of point_aggregators.py:276-348 for the lego flag set
-        self.block1 = nn.Sequential(nn.Linear(284, 256), mk(), nn.Linear(256, 256), mk())
+        # shapes of point_aggregators.py:276-348: block1.0 takes [emb, PE_3(emb)] (7E) + PE_5 of the
+        # 6-d distance (60); its point half ends at column self.split (224 for the lego E = 32)
+        self.E = int(getattr(opt, "point_features_dim", 32))
+        self.order = int(getattr(opt, "agg_intrp_order", 2))
+        self.split = 7 * self.E
+        self.block1 = nn.Sequential(nn.Linear(self.split + 60, 256), mk(), nn.Linear(256, 256), mk())
         self.block3 = nn.Sequential(nn.Linear(263, 256), mk(), nn.Linear(256, 256), mk())
         self.alpha_branch = nn.Sequential(nn.Linear(256, 1))
         self.C = int(getattr(opt, "shading_color_channel_num", 128))
@@ -310,7 +337,7 @@ class PointAggregator(nn.Module):
     def _fp32_specs(self) -> list:
         """(name, W, bias) of the native-fp32 packs of packed()."""
         b1, b3, cb = self.block1, self.block3, self.color_branch
-        return [("w1af", b1[0].weight[:, :224], b1[0].bias), ("w1bf", b1[0].weight[:, 224:], None),
+        return [("w1af", b1[0].weight[:, :self.split], b1[0].bias), ("w1bf", b1[0].weight[:, self.split:], None),
                 ("w2f", b1[2].weight, b1[2].bias), ("w3f", b3[0].weight, b3[0].bias),
                 ("w4f", b3[2].weight, b3[2].bias), ("wc1f", cb[0].weight, cb[0].bias),
                 ("wc2f", cb[2].weight, cb[2].bias), ("wc3f", cb[4].weight, cb[4].bias)]
@@ -327,6 +354,7 @@ class PointAggregator(nn.Module):
             setattr(m, k, v.data_ptr())
         m.neg_slope = float(self.neg_slope)
         m.act_super = self.act_super
+        m.intrp_order = self.order
         self._packed, self._packed_key = (m, t), key
         return self._packed
 
@@ -346,6 +374,7 @@ class PointAggregator(nn.Module):
         changed (every step: the optimizer moved them); bitwise the packs of the
         per-matrix calls.  Afterwards packed() / packed_h2_train() return them
         from their caches."""
+        require_default_dims(self.opt, "the training packs")
         dev = self.block1[0].weight.device
         if dev.type != "cuda":
             return
@@ -386,6 +415,7 @@ class PointAggregator(nn.Module):
 
     def packed_bf16(self) -> tuple[L.MlpBf16, dict]:
         """bf16 fragment packs for pnr_aggregate_fwd_bf16 (cached like packed())."""
+        require_default_dims(self.opt, "the bf16 aggregate")
         ps = list(self.parameters())
         key = tuple((p.data_ptr(), p._version) for p in ps) + ((self.rw2c.data_ptr(), self.rw2c._version),
                                                                 bool(self.pair_buckets))
@@ -393,8 +423,8 @@ class PointAggregator(nn.Module):
             return self._packed16
         with torch.no_grad():
             b1, b3, cb = self.block1, self.block3, self.color_branch
-            t = dict(w1af=frag_pack_bf16(b1[0].weight[:, :224], b1[0].bias),
-                     w1bf=frag_pack_bf16(b1[0].weight[:, 224:]),
+            t = dict(w1af=frag_pack_bf16(b1[0].weight[:, :self.split], b1[0].bias),
+                     w1bf=frag_pack_bf16(b1[0].weight[:, self.split:]),
                      w2f=frag_pack_bf16(b1[2].weight, b1[2].bias), w3f=frag_pack_bf16(b3[0].weight, b3[0].bias),
                      w4f=frag_pack_bf16(b3[2].weight, b3[2].bias),
                      wa=self.alpha_branch[0].weight.float().reshape(-1).contiguous(),
@@ -411,7 +441,7 @@ class PointAggregator(nn.Module):
         return self._packed16
 
     def packed_x3(self) -> tuple[L.MlpX3, dict]:
-        """Split-bf16 packs of block1.0[:, 224:], block1.2, block3.0, block3.2
+        """Split-bf16 packs of block1.0[:, 7E:], block1.2, block3.0, block3.2
         for pnr_aggregate_fwd_x3 (used with packed(); cached like it)."""
         ps = list(self.parameters())
         key = tuple((p.data_ptr(), p._version) for p in ps)
@@ -419,14 +449,14 @@ class PointAggregator(nn.Module):
             return self._packedx3
         with torch.no_grad():
             b1, b3 = self.block1, self.block3
-            t = dict(w1bx=frag_pack_x3(b1[0].weight[:, 224:]), w2x=frag_pack_x3(b1[2].weight, b1[2].bias),
+            t = dict(w1bx=frag_pack_x3(b1[0].weight[:, self.split:]), w2x=frag_pack_x3(b1[2].weight, b1[2].bias),
                      w3x=frag_pack_x3(b3[0].weight, b3[0].bias), w4x=frag_pack_x3(b3[2].weight, b3[2].bias))
         m = L.MlpX3(*(t[k].data_ptr() for k in ("w1bx", "w2x", "w3x", "w4x")))
         self._packedx3, self._packedx3_key = (m, t), key
         return self._packedx3
 
     def packed_h2(self) -> tuple[L.MlpH2, dict]:
-        """Split-f16 packs of block1.0[:, 224:], block1.2, block3.0, block3.2
+        """Split-f16 packs of block1.0[:, 7E:], block1.2, block3.0, block3.2
         for pnr_aggregate_fwd_h2 (used with packed(); cached like it).  The
         dict holds the device range flag (`range_flag`, int32[1])."""
         key = self.h2_key()
@@ -436,7 +466,7 @@ class PointAggregator(nn.Module):
             b1, b3, cb = self.block1, self.block3, self.color_branch
             # block1.2 / block3.2 without the bias column: k_pairs_h2 starts their
             # accumulators at bias / scale (pnr_mlp b2 / b4)
-            packs = [frag_pack_h2(b1[0].weight[:, 224:]), frag_pack_h2(b1[2].weight),
+            packs = [frag_pack_h2(b1[0].weight[:, self.split:]), frag_pack_h2(b1[2].weight),
                      frag_pack_h2(b3[0].weight, b3[0].bias), frag_pack_h2(b3[2].weight)]
             # colour layer 1 in two 144-row halves sharing one scale (k_color_h2)
             s1 = h2_shift(cb[0].weight, cb[0].bias)
@@ -444,7 +474,7 @@ class PointAggregator(nn.Module):
                       frag_pack_h2(cb[0].weight[:, 144:], cb[0].bias, shift=s1),
                       frag_pack_h2(cb[2].weight, cb[2].bias), frag_pack_h2(cb[4].weight, cb[4].bias)]
             # block1.0's per-point half (k_point_pre_h2)
-            p1pack = frag_pack_h2(b1[0].weight[:, :224], b1[0].bias)
+            p1pack = frag_pack_h2(b1[0].weight[:, :self.split], b1[0].bias)
         flag = torch.zeros(1, dtype=torch.int32, device=b1[0].weight.device)
         t = dict(w1bh=packs[0][0], w2h=packs[1][0], w3h=packs[2][0], w4h=packs[3][0], range_flag=flag,
                  wc1a=cpacks[0][0], wc1b=cpacks[1][0], wc2h=cpacks[2][0], wc3h=cpacks[3][0], w1ah=p1pack[0])
@@ -457,7 +487,7 @@ class PointAggregator(nn.Module):
         return self._packedh2
 
     def packed_h2_train(self) -> tuple[L.MlpH2, dict]:
-        """fp32h2 packs of the per-pair chain (block1.0[:, 224:], block1.2,
+        """fp32h2 packs of the per-pair chain (block1.0[:, 7E:], block1.2,
         block3.0, block3.2) and of block1.0's point half (P1 on k_point_pre_h2)
         for pnr_aggregate_fwd_train_h2, packed on the device
         (pnr_pack_weights_h2: no host sync while the weights change every step)
@@ -465,6 +495,7 @@ class PointAggregator(nn.Module):
         the pack when a weight outgrew its shift and by the forward when an
         activation left the f16 range -- the guarded forward then runs its
         fp32 fallback on the device, and h2_train_poll() re-picks the shifts."""
+        require_default_dims(self.opt, "the fp32h2 training packs")
         key = self.h2_key()
         if getattr(self, "_packedh2t", None) is not None and key == self._packedh2t_key:
             return self._packedh2t
@@ -475,8 +506,8 @@ class PointAggregator(nn.Module):
 
     def _h2t_mats(self) -> list:
         b1, b3, cb = self.block1, self.block3, self.color_branch
-        mats = [(b1[0].weight[:, 224:], None), (b1[2].weight, None), (b3[0].weight, b3[0].bias), (b3[2].weight, None),
-                (b1[0].weight[:, :224], b1[0].bias)]   # then: block1.0's point half (k_point_pre_h2)
+        mats = [(b1[0].weight[:, self.split:], None), (b1[2].weight, None), (b3[0].weight, b3[0].bias), (b3[2].weight, None),
+                (b1[0].weight[:, :self.split], b1[0].bias)]   # then: block1.0's point half (k_point_pre_h2)
         if H2_TRAIN_COLOR:   # the colour branch (k_color_h2<true>): layer 1 in two halves of one shift
             mats += [(cb[0].weight[:, :144], None), (cb[0].weight[:, 144:], cb[0].bias), (cb[2].weight, cb[2].bias),
                      (cb[4].weight, cb[4].bias)]
@@ -622,6 +653,7 @@ class PointAggregator(nn.Module):
         if torch.is_grad_enabled() and (any(t.requires_grad for t in diff) or
                                         any(p.requires_grad for p in self.parameters())):
             # training path: autograd through pnr_aggregate_fwd_train / _bwd_pairs (train.py)
+            require_default_dims(self.opt, "PointAggregator.forward with gradients (training)")
             from .train import AggSpec, AggregateFn, PointTables, agg_params
             spec = AggSpec(self, s, rows, PointTables(keep["xyz"], pers=keep["pers"], rw2c=rw_pairs),
                            pair_mask=keep["mask"], keep=(keep, rw_pairs))
@@ -633,11 +665,12 @@ class PointAggregator(nn.Module):
             out = out[:rows]
         else:
             out = torch.zeros((rows, C + 1), dtype=torch.float32, device=dev)
-            keep.update(emb=flat(sampled_embedding, 32), color=flat(sampled_color, 3), dir=flat(sampled_dir, 3),
+            keep.update(emb=flat(sampled_embedding, self.E), color=flat(sampled_color, 3), dir=flat(sampled_dir, 3),
                         conf=flat(sampled_conf, 1))
             pts = L.Points(rows * K, keep["xyz"].data_ptr(), keep["pers"].data_ptr(), keep["emb"].data_ptr(),
                            L.ptr(keep["color"]), L.ptr(keep["dir"]), L.ptr(keep["conf"]), None, None)
             pts.rw2c = L.ptr(rw_pairs)
+            pts.emb_dim = self.E
             mlp, _ = self.packed()
             scratch = L.aggregate_scratch(rows, rows * K, dev)
             L.check(L.lib().pnr_aggregate_fwd_masked(L.ctypes.byref(pts), L.ctypes.byref(s),

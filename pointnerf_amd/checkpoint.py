@@ -3,7 +3,7 @@
 ``{epoch}_net_ray_marching.pth`` holds the state_dict of the reference's
 NeuralPointsRayMarching (base_model.py:99-116 save_networks): the point table
 under ``neural_points.*`` (neural_points.py:241-326: xyz [N,3],
-points_embeding [1,N,32], points_conf [1,N,1], points_dir [1,N,3],
+points_embeding [1,N,E] (E = point_features_dim), points_conf [1,N,1], points_dir [1,N,3],
 points_color [1,N,3], optional Rw2c / eulers) and the aggregator under
 ``aggregator.*`` (point_aggregators.py:276-348).  ``pointnerf_amd`` uses the same
 module tree and parameter names, so the reference files load here and files
@@ -40,6 +40,13 @@ def load_ray_marching(path: str, opt, device, epoch_is_best: bool = False) -> Ne
     if "xyz" not in np_sd or "points_embeding" not in np_sd:
         raise L.PnrError(f"{path}: no neural_points.xyz / neural_points.points_embeding")
     xyz = np_sd["xyz"].float().reshape(-1, 3)
+    e_file, e_opt = int(np_sd["points_embeding"].shape[-1]), int(getattr(opt, "point_features_dim", 32))
+    if e_file != e_opt:
+        raise L.PnrError(f"{path}: neural_points.points_embeding is {e_file} wide, opt.point_features_dim is {e_opt}")
+    w1 = sd.get("aggregator.block1.0.weight")
+    if w1 is not None and w1.shape[-1] != 7 * e_opt + 60:
+        raise L.PnrError(f"{path}: aggregator.block1.0.weight has {w1.shape[-1]} inputs (point_features_dim "
+                         f"{(w1.shape[-1] - 60) // 7}), opt.point_features_dim {e_opt} needs {7 * e_opt + 60}")
     n = xyz.shape[0]
     conf = np_sd.get("points_conf")
     dc = float(getattr(opt, "default_conf", -1.0))

@@ -225,6 +225,26 @@ int launch_pairs_split(const pnr_points& pts, const pnr_samples& s, const pnr_ml
 // x1 (training, optional): the input rows [emb, PE_3(emb)] are written there too
 int launch_point_pre_h2(const pnr_points& pts, const void* pack, float scale, int32_t* range_flag, float* p1,
                         hipStream_t st, float* x1 = nullptr);
+// The DTU configuration (ABI 31).  emb_width: floats per
+// row of pnr_points.emb (emb_dim, 0 = 32).  The per-point pass for any width in
+// 1..64: k_point_pre_w (aggregate_wide.hip, fp32 MFMA; w1af = frag_pack of
+// W1[:, :7E] + b1) and k_point_pre_h2_w (aggregate_x3.hip, f16-split; pack =
+// frag_pack_h2 of the same).  launch_tail_o1: agg_intrp_order 1's tail after the
+// colour kernel (aggregate_wide.hip); planes: hid still in k_pairs_h2's planes.
+__host__ __device__ inline int emb_width(const pnr_points& p) { return p.emb_dim ? p.emb_dim : kEmb; }
+inline bool default_dims(const pnr_points* p, const pnr_mlp* w) {
+  return (!p || p->emb_dim == 0 || p->emb_dim == kEmb) && (!w || w->intrp_order == 0 || w->intrp_order == 2);
+}
+// an entry point that knows only point_features_dim 32 / agg_intrp_order 2
+#define PNR_CHECK_DEFAULT_DIMS(who, pts, w)                                                                  \
+  PNR_CHECK_ARG(::pnr::default_dims(pts, w),                                                                 \
+                "%s: pnr_points.emb_dim (point_features_dim) must be 0 or 32 and pnr_mlp.intrp_order "      \
+                "(agg_intrp_order) 0 or 2 here", who)
+int launch_point_pre_w(const pnr_points& pts, const float* w1af, float* p1, hipStream_t st);
+int launch_point_pre_h2_w(const pnr_points& pts, const void* pack, float scale, int32_t* range_flag, float* p1,
+                          hipStream_t st);
+int launch_tail_o1(const pnr_samples& s, const pnr_mlp& w, const float* hid, bool planes, const int32_t* vmask,
+                   float* out_feat, hipStream_t st);
 // Workgroup barrier for an LDS hand-off only: lgkmcnt(0) + s_barrier between
 // LDS-scoped fences, so the compiler keeps LDS accesses on their side while
 // global loads stay in flight across it (__syncthreads' fence drains them with

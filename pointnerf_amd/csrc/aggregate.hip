@@ -765,7 +765,13 @@ static int check_common(const pnr_points* pts, const pnr_samples* s, const pnr_m
   PNR_CHECK_ARG(w->w1af && w->w1bf && w->w2f && w->b2 && w->w3f && w->b3 && w->w4f && w->b4 && w->wa &&
                     w->ba && w->wc1f && w->bc1 && w->wc2f && w->bc2 && w->wc3f && w->bc3,
                 "aggregate: null weight");
-  PNR_CHECK_ARG(((uintptr_t)pts->emb & 15) == 0, "aggregate: emb must be 16-B aligned");
+  PNR_CHECK_ARG(pts->emb_dim >= 0 && pts->emb_dim <= 64, "aggregate: emb_dim %d unsupported (1..64, 0 = 32)",
+                pts->emb_dim);
+  PNR_CHECK_ARG(w->intrp_order >= 0 && w->intrp_order <= 2, "aggregate: intrp_order %d unsupported (0, 1, 2)",
+                w->intrp_order);
+  // the wide per-point kernels read emb with dword loads; the 32-wide ones with b128
+  PNR_CHECK_ARG(((uintptr_t)pts->emb & (emb_width(*pts) == kEmb ? 15 : 3)) == 0,
+                "aggregate: emb must be 16-B aligned (4-B with emb_dim != 32)");
   PNR_CHECK_ARG(scratch && ((uintptr_t)scratch & 15) == 0, "aggregate: 16-B aligned scratch required");
   PNR_CHECK_ARG(pts->n > 0, "aggregate: empty point table");
   PNR_CHECK_ARG(!pts->used || (pts->used_map && pts->n_used >= 0 && pts->n_used <= pts->n),
@@ -860,6 +866,7 @@ static int aggregate_forward(const FwdCall& c, const pnr_points* pts, const pnr_
   // ---- every refusal, before the first launch
   PNR_CHECK_ARG(!guarded || (c.wh && c.wh->range_flag), "%s: range_flag required", c.who);
   if ((rc = check_common(pts, s, w, out_feat, scratch, scratch_bytes))) return rc;
+  if (c.train()) PNR_CHECK_DEFAULT_DIMS(c.who, pts, w);   // the training kernels: E = 32, order 2
   if (c.train() && (rc = check_saved(c.saved))) return rc;
   if (c.flags & kMasked) {
     PNR_CHECK_ARG(c.pair_mask, "%s: null pair_mask", c.who);
@@ -898,11 +905,30 @@ static int aggregate_forward(const FwdCall& c, const pnr_points* pts, const pnr_
   auto fp32 = [&](const AggArgs& x, int stages) {
     return c.train() ? launch_t<true>(x, st, stages) : launch_t<false>(x, st, stages);
   };
+  // agg_intrp_order 1 (inference only, checked above): k_tail_o1 behind the colour kernel.
+  // planes: hid still in k_pairs_h2's f16-split planes (the colour branch ran on k_color_h2)
+  auto tail = [&](int rc0, bool planes) {
+    if (rc0 || w->intrp_order != 1) return rc0;
+    return launch_tail_o1(a.s, a.w, a.hid, planes, a.vmask, out_feat, st);
+  };
+  // point_features_dim != 32 (inference only): P1 from the wide per-point kernels
+  // (aggregate_wide.hip, k_point_pre_h2_w); every later stage reads P1 rows only
+  const bool wide = emb_width(*pts) != kEmb;
 
   // ---- the stages
-  if (c.arith == Arith::F32) return fp32(a, kStageAll);   // k_point_pre -> k_pairs -> k_color
+  if (c.arith == Arith::F32) {   // k_point_pre -> k_pairs -> k_color
+    if (!wide) return tail(fp32(a, kStageAll), false);
+    if (!a.pts.p1_ready && (rc = launch_point_pre_w(a.pts, w->w1af, a.p1, st))) return rc;
+    return tail(fp32(a, kStagePairs | kStageColor), false);
+  }
   // P1: k_point_pre_h2 with wh->w1ah, else the fp32 k_point_pre; skipped on pts->p1_ready
-  if (h2 && c.wh->w1ah) {
+  if (wide) {
+    if (a.pts.p1_ready) rc = PNR_OK;
+    else if (h2 && c.wh->w1ah)
+      rc = launch_point_pre_h2_w(a.pts, c.wh->w1ah, c.wh->scale1a, c.wh->range_flag, a.p1, st);
+    else rc = launch_point_pre_w(a.pts, w->w1af, a.p1, st);
+    if (rc) return rc;
+  } else if (h2 && c.wh->w1ah) {
     if ((c.train() || !a.pts.p1_ready) &&
         (rc = launch_point_pre_h2(a.pts, c.wh->w1ah, c.wh->scale1a, c.wh->range_flag, a.p1, st,
                                   c.train() ? c.saved->x1 : nullptr)))
@@ -936,11 +962,11 @@ static int aggregate_forward(const FwdCall& c, const pnr_points* pts, const pnr_
     const void* cp[4] = {c.wh->wc1a, c.wh->wc1b, c.wh->wc2h, c.wh->wc3h};
     rc = launch_color_h2(a.s, a.w, cp, c.wh->cscale, c.wh->range_flag, a.hid, a.vmask, out_feat, st, a.pts.rw2c,
                          c.saved);
-    return rc || !guarded ? rc : launch_t<true>(f, st, kStageColor);
+    return rc || !guarded ? tail(rc, true) : launch_t<true>(f, st, kStageColor);
   }
   // the inference k_pairs_h2 leaves hid as f16-split planes (k_color_h2's input): rows for k_color
   if (h2 && !c.train() && (rc = launch_hid_rows_h2(a.hid, s->n_max, st))) return rc;
-  return fp32(a, kStageColor);
+  return tail(fp32(a, kStageColor), false);
 }
 
 }  // namespace pnr
@@ -979,12 +1005,18 @@ extern "C" int pnr_point_pre_h2(const pnr_points* pts, const pnr_mlp_h2* wh, voi
   int rc;
   PNR_CHECK_ARG(pts && wh && pts->emb && scratch, "point_pre_h2: null pointer");
   if ((rc = check_p1_h2("point_pre_h2", wh))) return rc;
-  PNR_CHECK_ARG(((uintptr_t)pts->emb & 15) == 0 && ((uintptr_t)scratch & 15) == 0,
-                "point_pre_h2: emb and scratch must be 16-B aligned");
+  PNR_CHECK_ARG(pts->emb_dim >= 0 && pts->emb_dim <= 64, "point_pre_h2: emb_dim %d unsupported (1..64, 0 = 32)",
+                pts->emb_dim);
+  const bool wide = emb_width(*pts) != kEmb;
+  PNR_CHECK_ARG(((uintptr_t)pts->emb & (wide ? 3 : 15)) == 0 && ((uintptr_t)scratch & 15) == 0,
+                "point_pre_h2: emb and scratch must be 16-B aligned (emb: 4-B with emb_dim != 32)");
   const int64_t n_p1 = pts->used ? pts->n_used : pts->n;
   PNR_CHECK_ARG(n_p1 >= 0 && scratch_bytes >= (size_t)(n_p1 > 0 ? n_p1 : 1) * kHid * sizeof(float),
                 "point_pre_h2: scratch too small for the P1 rows");
   if (n_p1 == 0) return PNR_OK;
+  if (wide)
+    return launch_point_pre_h2_w(*pts, wh->w1ah, wh->scale1a, wh->range_flag, static_cast<float*>(scratch),
+                                 as_stream(stream));
   return launch_point_pre_h2(*pts, wh->w1ah, wh->scale1a, wh->range_flag, static_cast<float*>(scratch),
                              as_stream(stream));
 }

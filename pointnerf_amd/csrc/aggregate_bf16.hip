@@ -843,6 +843,7 @@ static int aggregate_fwd_bf16(const pnr_points* pts, const pnr_samples* s, const
                               uint16_t* out_feat_h, float* out_weight, float* out_conf, void* scratch,
                               size_t scratch_bytes, void* stream) {
   PNR_CHECK_ARG(pts && s && w && (out_feat || out_feat_h), "aggregate_bf16: null pointer");
+  PNR_CHECK_DEFAULT_DIMS("aggregate_bf16", pts, nullptr);
   PNR_CHECK_ARG(((uintptr_t)out_feat_h & 15) == 0, "aggregate_bf16_hf: out_feat_h must be 16-B aligned");
   PNR_CHECK_ARG(pts->xyz && (pts->emb || pts->emb_bf16) && s->pidx, "aggregate_bf16: point xyz/emb and pidx required");
   PNR_CHECK_ARG(s->sample_w && s->sample_p && s->dirs && s->dir_div >= 1, "aggregate_bf16: sample arrays required");

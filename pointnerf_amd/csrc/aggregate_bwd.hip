@@ -828,6 +828,7 @@ static int bwd_pairs(const pnr_points* pts, const pnr_samples* s, const pnr_mlp*
                      float* d_color, float* d_dir, float* d_conf, void* stream) {
   int rc;
   PNR_CHECK_ARG(pts && s && w && wb, "aggregate_bwd: null pointer");
+  PNR_CHECK_DEFAULT_DIMS("aggregate_bwd", pts, w);
   if ((rc = check_saved(saved))) return rc;
   PNR_CHECK_ARG((wb->w3e || wbx || wbh) && w->wa && (wbx || wbh || (wb->w4t && wb->w3t && wb->w2t)),
                 "aggregate_bwd: null weight");
@@ -921,6 +922,7 @@ extern "C" int pnr_aggregate_bwd_xyz(const pnr_points* pts, const pnr_samples* s
                                      const pnr_agg_saved* saved, const float* d_feat, const float* d_hid,
                                      const float* d_pe, float* d_xyz, void* stream) {
   PNR_CHECK_ARG(pts && s && w && saved && d_feat && d_hid && d_pe && d_xyz, "aggregate_bwd_xyz: null argument");
+  PNR_CHECK_DEFAULT_DIMS("aggregate_bwd_xyz", pts, w);
   PNR_CHECK_ARG(pts->xyz && pts->campos && pts->camrot, "aggregate_bwd_xyz: need xyz and the camera tables");
   PNR_CHECK_ARG(saved->prow && saved->pa && saved->h4 && saved->pe5 && saved->vmask,
                 "aggregate_bwd_xyz: missing saved activations");
@@ -944,6 +946,7 @@ extern "C" int pnr_aggregate_bwd_extras_rows(const pnr_points* pts, const pnr_sa
                                              const pnr_agg_saved* saved, const float* w3e, const float* dz3,
                                              float* g_pair, void* stream) {
   PNR_CHECK_ARG(pts && s && w && saved && saved->prow && w3e, "aggregate_bwd_extras_rows: null pointer");
+  PNR_CHECK_DEFAULT_DIMS("aggregate_bwd_extras_rows", pts, w);
   PNR_CHECK_ARG(s->n_max == 0 || (dz3 && g_pair && (((uintptr_t)dz3 | (uintptr_t)g_pair) & 15) == 0),
                 "aggregate_bwd_extras_rows: dz3 / g_pair must be 16-B aligned");
   PNR_CHECK_ARG(s->dirs && s->dir_div >= 1, "aggregate_bwd_extras_rows: sample dirs required");

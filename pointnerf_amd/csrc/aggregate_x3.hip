@@ -1597,7 +1597,123 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   if (A.range_flag && chk != 0.f) atomicOr(A.range_flag, 1);
 }
 
+// k_point_pre_h2 for an embedding table of any width E in 1..64 (pnr_points.emb_dim,
+// DESIGN.md section 31): P1[p] = W1[:, :7E] . [emb_p, PE_3(emb_p)] + b1 in ONE pass
+// of nsteps = ceil((7E + 1) / 16) k-steps over planes [2][2 nsteps row groups][64
+// points][8] (E = 63: 28 steps, 112 KB, one workgroup per CU).  Rows in the
+// reference's order (networks.py:175-190): emb 0..E-1, PE E + 6c + {sin, cos} x 3
+// bands (angle doubling as k_point_pre), bias row 7E, zeros up to 16 nsteps.
+// Thread (point lane, wid) takes the channels c = wid (mod 4); a row of E floats
+// is only 4-B aligned, so emb is read with dword loads and each row's two f16
+// halves are stored on their own (ds_write_b16).
+struct P1H2WArgs {
+  pnr_points pts;
+  const void* pack;     // W1[:, :7E] + b1, frag_pack_h2
+  float scale;
+  int32_t* range_flag;
+  float* p1;
+  int E;
+};
+
+__device__ __forceinline__ void store_row_h2(char* planes, int pstride, int r, int pair, float v) {
+  const _Float16 hi = (_Float16)v;
+  const _Float16 lo = (_Float16)((v - (float)hi) * 2048.f);   // splith's halves
+  char* d = planes + ((r >> 3) * kXT + pair) * 16 + (r & 7) * 2;
+  *reinterpret_cast<_Float16*>(d) = hi;
+  *reinterpret_cast<_Float16*>(d + pstride) = lo;
+}
+
+__global__ void __launch_bounds__(256) k_point_pre_h2_w(P1H2WArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int c = lane & 31, h = lane >> 5;
+  const int E = A.E;
+  const int nsteps = (7 * E + 1 + 15) >> 4;
+  const int plane = 2 * nsteps * kXT * 16;   // bytes per f16 plane
+  const int64_t np = p1_rows(A.pts);   // P1 rows
+  const int64_t ntiles = cdiv(np, kXT);
+  const int T0 = 2 * wid;
+  const int voff = (T0 * XL<true>::NPW * 64 + lane) * 16;
+  const __amdgpu_buffer_rsrc_t rw = rsrc(A.pack);
+  float chk = 0.f;   // 0 * outputs: NaN once one is not finite (an input beyond the f16 range)
+  WRing<true> wr;
+  f32x16 acc[4], corr[4];
+  prime<true>(wr, rw, voff);
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    {
+      const int64_t pt = tile * kXT + lane;
+      const bool act = pt < np;
+      const int64_t prow = act ? (A.pts.used ? (int64_t)A.pts.used[pt] : pt) : 0;
+      const float* e = A.pts.emb + prow * E;
+#pragma unroll 1
+      for (int ch = wid; ch < E; ch += 4) {
+        const float ev = act ? e[ch] : 0.f;
+        float s0, c0;
+        sincosf(ev, &s0, &c0);
+        const float s1 = 2.f * s0 * c0, c1 = (c0 - s0) * (c0 + s0);
+        const float s2 = 2.f * s1 * c1, c2 = (c1 - s1) * (c1 + s1);
+        const int r0 = E + 6 * ch;
+        store_row_h2(lds, plane, ch, lane, ev);
+        store_row_h2(lds, plane, r0, lane, s0);
+        store_row_h2(lds, plane, r0 + 1, lane, c0);
+        store_row_h2(lds, plane, r0 + 2, lane, s1);
+        store_row_h2(lds, plane, r0 + 3, lane, c1);
+        store_row_h2(lds, plane, r0 + 4, lane, s2);
+        store_row_h2(lds, plane, r0 + 5, lane, c2);
+      }
+      // row 7E = 1 (bias column), the rest of the last k-step = 0
+      for (int r = 7 * E + wid; r < 16 * nsteps; r += 4) store_row_h2(lds, plane, r, lane, r == 7 * E ? 1.f : 0.f);
+    }
+    __syncthreads();
+    layer<true, 8, true, true>(acc, corr, wr, rw, voff, lds, plane, nsteps, lane);
+    prime<true>(wr, rw, voff);   // the next tile
+#pragma unroll
+    for (int pt = 0; pt < 2; ++pt) {
+      const int64_t prow = tile * kXT + 32 * pt + c;   // P1 row (index into used when set)
+#pragma unroll
+      for (int T = 0; T < 2; ++T)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x16& m = acc[2 * pt + T];
+          const f32x16& r = corr[2 * pt + T];   // two accumulator sets: scale (2048 main + corr)
+          const float4 o = make_float4(fold2(m[4 * q], r[4 * q]) * A.scale, fold2(m[4 * q + 1], r[4 * q + 1]) * A.scale,
+                                       fold2(m[4 * q + 2], r[4 * q + 2]) * A.scale,
+                                       fold2(m[4 * q + 3], r[4 * q + 3]) * A.scale);
+          chk = fmaf(0.f, (o.x + o.y) + (o.z + o.w), chk);
+          if (prow < np)
+            *reinterpret_cast<float4*>(A.p1 + prow * kHid + 32 * (T0 + T) + 8 * q + 4 * h) = o;
+        }
+    }
+    __syncthreads();   // the planes are rewritten by the next tile
+  }
+  if (A.range_flag && chk != 0.f) atomicOr(A.range_flag, 1);
+}
+
 }  // namespace
+
+int launch_point_pre_h2_w(const pnr_points& pts, const void* pack, float scale, int32_t* range_flag, float* p1,
+                          hipStream_t st) {
+  static bool attr = false;
+  const int E = emb_width(pts);
+  if (!attr) {
+    PNR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_point_pre_h2_w),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 29 * kXT * 16));
+    attr = true;
+  }
+  P1H2WArgs a;
+  a.pts = pts;
+  a.pack = pack;
+  a.scale = scale;
+  a.range_flag = range_flag;
+  a.p1 = p1;
+  a.E = E;
+  const int nsteps = (7 * E + 1 + 15) >> 4;   // <= 29 (E = 64)
+  const int64_t np = pts.used ? pts.n_used : pts.n;
+  hipLaunchKernelGGL(k_point_pre_h2_w, dim3(grid_for(cdiv(np, kXT), 1, 256)), dim3(256),
+                     (size_t)2 * 2 * nsteps * kXT * 16, st, a);
+  PNR_LAUNCH_CHECK();
+  return PNR_OK;
+}
 
 int launch_point_pre_h2(const pnr_points& pts, const void* pack, float scale, int32_t* range_flag, float* p1,
                         hipStream_t st, float* x1) {

@@ -156,6 +156,8 @@ extern "C" int pnr_probe(const pnr_rays* rays, const pnr_query_params* q, const 
                          void* stream) {
   PNR_CHECK_ARG(rays && q && b && pts && opacity && max_opacity && max_loc_w && far_dist && avg_emb,
                 "probe: null pointer");
+  PNR_CHECK_ARG(pts->emb_dim == 0 || pts->emb_dim == 32,
+                "probe: pnr_points.emb_dim (point_features_dim) must be 0 or 32 here");
   PNR_CHECK_ARG(q->SR >= 1 && q->SR <= 128, "probe: SR=%d unsupported (1..128)", q->SR);
   PNR_CHECK_ARG(q->K >= 1 && q->K <= 16, "probe: K=%d unsupported (1..16)", q->K);
   PNR_CHECK_ARG(b->n_filled && b->ray_off && b->ray_vcnt && b->pidx && b->sample_w, "probe: null query buffer");

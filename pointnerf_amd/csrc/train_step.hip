@@ -418,6 +418,7 @@ extern "C" int pnr_aggregate_bwd_step_h2(const pnr_points* pts, const pnr_sample
                                          size_t scratch_bytes, void* stream) {
   PNR_CHECK_ARG(pts && s && w && prm && saved && out && scratch && n >= 0 && n_used >= 0,
                 "aggregate_bwd_step_h2: null pointer or negative count");
+  PNR_CHECK_DEFAULT_DIMS("aggregate_bwd_step_h2", pts, w);
   PNR_CHECK_ARG(pts->used && pts->used_map && pts->emb, "aggregate_bwd_step_h2: the used-point list is required");
   PNR_CHECK_ARG(saved->dz_absmax && saved->prow && saved->h1 && saved->hid && saved->vpe && saved->hc1 &&
                     saved->hc2 && saved->hc3 && saved->vmask && saved->pe5 && saved->x3e,

@@ -74,6 +74,22 @@ def dtu_opt(**over):
     return lego_opt(**o)
 
 
+# The aggregator flags those six scripts pass on top of DTU: 63-channel point features assembled from
+# [colour, dir, conf, feat] (the three modes "01": in the embedding and kept as tables), conf fixed to 1;
+# the five dtu_test_inf scripts add agg_intrp_order 1, the ete script keeps order 2.
+DTU_SCRIPT = dict(point_features_dim=63, point_conf_mode="01", point_dir_mode="01", point_color_mode="01",
+                  agg_intrp_order=1, default_conf=1)
+
+
+def dtu_script_opt(**over):
+    """dtu_opt() plus the DTU scripts' aggregator flags (DTU_SCRIPT): dev_scripts/dtu_test_inf/*.sh as it
+    stands, dev_scripts/ete/dtu_dgt_d012_img0123_conf_color_dir_agg2.sh as dtu_script_opt(agg_intrp_order=2).
+    Evaluation only."""
+    o = dict(DTU_SCRIPT)
+    o.update(over)
+    return dtu_opt(**o)
+
+
 def flagset_opt(name: str, **over):
     """Flag set of one reference scene script (FLAGSETS) plus overrides."""
     if name not in FLAGSETS:

@@ -6,6 +6,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
+from .aggregator import require_default_dims
 from .render_eval import bg_channels
 from .train import (AggregateFn, AggSpec, CompositeFn, CompositeSpec, PointTables, TRAIN_PRECISIONS, UsedPoints,
                     agg_params, used_points_device)
@@ -94,6 +95,7 @@ class _TrainCall:
 
     def __init__(self, model, campos, camrot, raydir, near, far, bg_color):
         self.m, self.np_, self.opt = model, model.neural_points, model.opt
+        require_default_dims(self.opt, "render_rays_train")   # before any launch: the training kernels are 32-wide, order 2
         if self.np_.points_embeding.dtype != torch.float32:
             raise L.PnrError("training needs an fp32 points_embeding (NeuralPoints(emb_dtype=torch.float32))")
         model._sync_rw2c()

@@ -34,7 +34,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .aggregator import PointAggregator
+from .aggregator import PointAggregator, require_default_dims
 from .losses import _SparseConfLoss, _ZeroOneConfLoss
 from .neural_points import NeuralPoints
 from .querier import camera_tables
@@ -261,6 +261,8 @@ class NeuralPointsRayMarching(nn.Module):
     def _render_rays(self, mode, precision, batch, state, **options):
         """One render call (render_eval._RenderCall and its modes) -> (outputs, its _PendingCall or None)."""
         self._world_only("render_rays / RenderGraph")   # the one door of every fused world render
+        if precision == "bf16":
+            require_default_dims(self.opt, "precision 'bf16'")
         return _RenderCall(self, mode, precision, batch, state, **options).run()
 
     def render_camera(self, campos, camrotc2w, intrinsic, H, W, near, far, bg_color, dir_norm=False, **kw):
@@ -346,6 +348,7 @@ class NeuralPointsRayMarching(nn.Module):
         render_train._TrainCall).  Returns ray_color
         [R,C] (requires grad w.r.t. points_embeding / color / dir / conf and the
         aggregator parameters), opacity [R,SR], is_bg [R], ray_mask [R]."""
+        require_default_dims(self.opt, "render_rays_train")
         self._world_only("render_rays_train")
         return _TrainCall(self, campos, camrot, raydir, near, far, bg_color).run()
 
@@ -380,6 +383,7 @@ class NeuralPointsRayMarching(nn.Module):
         the rendered opacity [R,SR] -- no compaction, no [R'',SR,K,*] tensors, no
         host read.  Shapes [1,R,1] / [1,R,3] / [1,R,32]; None for an absent
         point table; rows of rays without a neighbour are zeros."""
+        require_default_dims(self.opt, "probe_maps (opt.prob == 1, the point-growing probe)")
         self._world_only("probe_maps")
         np_ = self.neural_points
         raydir = raydir.reshape(-1, 3).float().contiguous()
@@ -488,6 +492,10 @@ class NeuralPointsRayMarching(nn.Module):
             any(p.requires_grad for p in self.parameters())
             or (torch.is_tensor(inputs.bg_color) and inputs.bg_color.requires_grad))
         prob = getattr(opt, "prob", 0) == 1
+        if train:
+            require_default_dims(opt, "forward: a training step")
+        if prob:
+            require_default_dims(opt, "opt.prob == 1 (the point-growing probe)")
         if not self.neural_points.perspective:
             if train and prob:
                 raise L.PnrError("opt.prob == 1 (the point-growing probe) is an evaluation render, as in the "
