@@ -25,8 +25,8 @@ kernels in the same order:
                        block3.0^T / block1.2^T, LeakyReLU masks, per-pair weight /
                        conf terms
   points_from_pairs    pnr_group_pairs, then the per-point sums in pair order (no
-                       float atomics): d conf, block1.0's per-point partial d P1 and,
-                       with a split chain, the block3.0 extras' d colour / d dir
+                       float atomics, on every chain): d conf, block1.0's per-point
+                       partial d P1 and the block3.0 extras' d colour / d dir
   pair_weight_grads    dW = dZ^T X over all pairs: block3.2, block3.0 (+ its extras
                        columns), block1.2, the alpha branch
   block1_point_half    dW1[:, :224] = dP1^T X1, dW1[:, 224:] = dz1^T PE_5,
@@ -88,8 +88,9 @@ class BwdPacks(NamedTuple):
 def packed_bwd(agg, chain: str, pairs_w3e: bool) -> BwdPacks:
     """Transposed fragment packs for the dX chain ("fp32" | "x3" | "h2"): native-fp32
     packs, split-bf16 packs, or the split-f16 packs of pnr_pack_bwd_h2 (one launch,
-    shifts picked on the device).  pairs_w3e: the pairs pass gets w3e (it then makes
-    the block3.0 extras' colour / dir gradients itself); else its w3e is NULL."""
+    shifts picked on the device).  pairs_w3e: the pairs pass gets w3e (given d colour /
+    d dir buffers it then makes the block3.0 extras' gradients itself, by float
+    atomics); else its w3e is NULL."""
     with torch.no_grad():
         W3 = agg.block3[0].weight
         t = dict(w3e=W3[:, 256:263].float().contiguous())
@@ -322,7 +323,7 @@ class _BwdPlan(NamedTuple):
     used: Any            # the referenced rows, cut to their count; None: block1.0's point half over the whole table
     chain: str           # the per-pair dX chain: "fp32" | "x3" | "h2" (_PAIRS)
     gemm: str            # the weight-gradient and colour-branch GEMMs: "x3" | "h2"
-    point_extras: bool   # block3.0 extras' d colour / d dir per point (pnr_pairs_to_points_ex), not in the pairs pass
+    point_extras: bool   # d colour / d dir wanted: block3.0's extras per point (pnr_pairs_to_points_ex)
     xyz: bool            # d xyz wanted
     native: bool         # the whole backward as pnr_aggregate_bwd_step_h2
 
@@ -348,7 +349,9 @@ class _BwdPlan(NamedTuple):
         xyz = ctx.xyz_shape is not None and ctx.needs_input_grad[5]
         # (a pair mask cannot come with a split chain: AggSpec refuses it)
         native = NATIVE_BWD and chain == "h2" and used is not None and not xyz
-        return cls(n, used, chain, gemm, chain != "fp32" and (has_c or has_d), xyz, native)
+        # d colour / d dir never come from the pairs pass (its float atomics made the fp32
+        # chain's differ from run to run): every chain sums them per point in pair order
+        return cls(n, used, chain, gemm, has_c or has_d, xyz, native)
 
 
 # chain -> entry point; the split chains take their split packs after the pnr_mlp_bwd
@@ -418,7 +421,7 @@ class _Backward:
 
     def pairs_chain(self):
         """The per-pair dX chain on MFMA: dz1..dz4 and d alpha-pre-activation per pair,
-        the per-pair d conf terms; with the fp32 chain also d colour / d dir."""
+        the per-pair d conf terms."""
         plan, f32, N = self.plan, self.f32, self.N
         has_c, has_d, has_f = self.ctx.has
         Pn = max(plan.n, 1) * 8
@@ -433,17 +436,18 @@ class _Backward:
         # the pairs' d conf terms, written per pair and summed per point in pair order by
         # pnr_pairs_to_points_conf (no float atomics: bitwise repeatable)
         self.dconf_pair = torch.empty(Pn, **f32) if has_f else None
-        # with point_extras the pairs pass gets no w3e: the block3.0 extras' colour / dir
-        # gradients are made per point in points_from_pairs (no float atomics)
-        self.packs = pk = packed_bwd(self.spec.agg, plan.chain, pairs_w3e=not plan.point_extras)
+        # the block3.0 extras' colour / dir gradients are made per point in points_from_pairs
+        # (no float atomics): the pairs pass gets no d colour / d dir, and no w3e either --
+        # except the fp32 kernel, which wants it bound
+        self.packs = pk = packed_bwd(self.spec.agg, plan.chain, pairs_w3e=plan.chain == "fp32")
         split = () if pk.split is None else (ctypes.byref(pk.split),)
         # d_p1 = NULL: the per-point sums of dz1 come from pnr_pairs_to_points (pairs
         # sorted by point: no atomics, deterministic) instead of the kernel's atomics
         entry = _PAIRS[plan.chain]
         L.check(getattr(L.lib(), entry)(*self._refs(), ctypes.byref(pk.mlp), *split, ctypes.byref(self.sv.c),
                                         L.ptr(self.d_feat), L.ptr(self.d_hid), *(L.ptr(t) for t in self.dz),
-                                        L.ptr(self.dpa), None, L.ptr(self.d_color), L.ptr(self.d_dir),
-                                        L.ptr(self.dconf_pair), L.stream_ptr(self.dev)), entry)
+                                        L.ptr(self.dpa), None, None, None, L.ptr(self.dconf_pair),
+                                        L.stream_ptr(self.dev)), entry)
 
     def points_from_pairs(self):
         """The pairs grouped by point in pair order (torch.sort(prow, stable=True)
@@ -521,13 +525,14 @@ class _Backward:
     def xyz(self):
         """d PE_5 = dz1 . W1[:, 224:284], then the distance / weight / w2pers chain per pair."""
         f32 = self.f32
-        w1pe = torch.zeros((256, 64), **f32)          # N padded to the GEMM's 32-column tiles
-        w1pe[:, :60] = self.P["block1.0.weight"][:, 224:284]
-        d_pe = L.gemm_nn(self.dz[0][:self.m], w1pe)
         d_xyz = torch.zeros((self.N, 3), **f32)
-        L.check(L.lib().pnr_aggregate_bwd_xyz(*self._refs(), ctypes.byref(self.sv.c), L.ptr(self.d_feat),
-                                              L.ptr(self.d_hid), L.ptr(d_pe), L.ptr(d_xyz), L.stream_ptr(self.dev)),
-                "pnr_aggregate_bwd_xyz")
+        if self.m > 0:   # (an empty list has no d PE_5 rows to hand over: d xyz stays 0)
+            w1pe = torch.zeros((256, 64), **f32)          # N padded to the GEMM's 32-column tiles
+            w1pe[:, :60] = self.P["block1.0.weight"][:, 224:284]
+            d_pe = L.gemm_nn(self.dz[0][:self.m], w1pe)
+            L.check(L.lib().pnr_aggregate_bwd_xyz(*self._refs(), ctypes.byref(self.sv.c), L.ptr(self.d_feat),
+                                                  L.ptr(self.d_hid), L.ptr(d_pe), L.ptr(d_xyz),
+                                                  L.stream_ptr(self.dev)), "pnr_aggregate_bwd_xyz")
         self.d_xyz = d_xyz.view(self.ctx.xyz_shape)
 
     def outputs(self) -> tuple:
