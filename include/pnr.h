@@ -1111,7 +1111,8 @@ int pnr_neural_render_bwd_h2(const float* x, const float* fwd_scratch, const flo
  *   out[v, 1 + j] = raw2out_color(sum_c w[j*128 + c] f_c + b[j]),  j < 3
  *   raw2out_color(x) = sigmoid(x) * (1 + 2e-3) - 1e-3 if act_super > 0, else sigmoid(x)
  * Backward: d_feat[v, 0] = d_out[v, 0], d_feat[v, 1 + c] = sum_j g_j w[j, c] for
- * the same rows (other rows untouched); d_wb[3, 129] = (d W | d b), written (not
+ * the same rows (other rows untouched); d_feat has feat's row stride ld (columns
+ * 129 .. ld - 1 untouched); d_wb[3, 129] = (d W | d b), written (not
  * accumulated): PNR_HEAD_BWD_BLOCKS workgroups write per-block partial sums into
  * the caller's partials[PNR_HEAD_BWD_BLOCKS * 3 * 129] floats, which a second
  * launch adds in block order (bitwise repeatable, no float atomics). */
