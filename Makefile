@@ -27,6 +27,8 @@ build/rays.o build/seed.o: HIPFLAGS += -ffp-contract=off
 build/fuse.o: HIPFLAGS += -ffp-contract=off
 # The perspective query's binning, centres and distances likewise.
 build/pquery.o: HIPFLAGS += -ffp-contract=off
+# The plane background's intersection, projections and fit bounds likewise.
+build/plane_bg.o: HIPFLAGS += -ffp-contract=off
 # The bf16 pair kernel's gather math (weights, distances, PE) without FMA
 # contraction: its render and general instantiations then round every fp32 op
 # the same way, so their features agree bit for bit (test_gpu_bf16.py).

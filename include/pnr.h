@@ -62,6 +62,12 @@
  *   pnr_pquery_compact   <- the perspective-frustum querier (--wcoord_query 0): get_occ_vox, near_vox_full,
  *                           insert_vox_points, query_neigh_along_ray_layered
  *                           models/neural_points/query_point_indices.py:265-413, 495-600
+ *   pnr_plane_fg_masks,
+ *   pnr_plane_bg         <- the per-ray background of bgmodel "plane": gen_bg_points / get_rayplane_cross,
+ *                           homo_warp_fg_mask, set_bg, fill_invalid
+ *                           models/mvs/mvs_utils.py:318-331, 380-408,
+ *                           models/mvs_points_volumetric_model.py:279-317,
+ *                           models/neural_points_volumetric_model_ori.py:109-111
  *   pnr_pquery_build,
  *   pnr_pquery_bufs,
  *   pnr_composite_fwd_p  <- the same querier plus pers2w (:104-116) and the module's ray_dist / ray_march /
@@ -79,7 +85,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 31
+#define PNR_ABI_VERSION 32
 
 enum {
   PNR_OK = 0,
@@ -1367,6 +1373,46 @@ int pnr_pquery_bufs(const pnr_pquery_params* params_host, int64_t N, const int32
 int pnr_composite_fwd_p(const pnr_query_params* q, const pnr_query_bufs* b, const pnr_composite_params* c, int64_t R,
                         const int8_t* ray_hit, float z_unfilled, const float* feat, float* ray_color, float* opacity,
                         float* is_bg, int8_t* ray_mask, void* stream);
+
+/* --------------------------------------------------- plane background (ABI 32)
+ * bg_ray of the reference's bgmodel "plane" on the camera table cams [F,16] and
+ * the images [F,H,W,3] (fp32, or uint8 read as / 255) of a frame set.  Camera
+ * coordinates c = Rc2w^T (p - campos) as in the seeding calls; the pixel position
+ * here is (u, v) = (cx / cz fx + cx0, cy / cz fy + cy0) with texel centres at the
+ * INTEGER coordinates (grid_sample's align_corners=True), and a position is in
+ * bounds when 0 <= u <= W - 1 and 0 <= v <= H - 1, both ends included.  There is
+ * no test of the sign of cz; a NaN or infinite position is out of bounds.  fp32,
+ * one rounding per operation.
+ *
+ * pnr_plane_fg_masks (homo_warp_fg_mask): for every point of xyz [N,3] and every
+ * view f in which it is in bounds, fg[f, ceil(v), ceil(u)] = 1.  Plain byte
+ * stores of the same value: the result does not depend on their order.  The
+ * caller zeroes fg [F,H,W] (uint8, fg_bytes >= F H W) first.  N = 0 launches
+ * nothing.
+ *
+ * pnr_plane_bg (gen_bg_points + set_bg): for each ray r of raydir [R,3] from
+ * campos [3] (device): dot = n . d; with dot >= 1e-3 the plane point is p = campos
+ * + d * (-(n . (campos - p0)) / dot) (the sign of the factor is not tested),
+ * otherwise p = (0, 0, 0), the world origin, which is projected like any other
+ * point.  For each view f: skip it when p is out of bounds or fg[f, ceil(v),
+ * ceil(u)] != 0; sample the image bilinearly at (u, v), the taps at x = W or y =
+ * H (reached at u = W - 1 or v = H - 1 only) counting as zero and never loaded;
+ * the sample fits when every channel lies in [plane_color - 0.03, plane_color +
+ * 0.03] (bounds formed in fp32, >= and <=).  bg[r, c] = the maximum over the
+ * fitting views of sample[c], 0 when none fits.  plane_pnt_host (p0),
+ * plane_normal_host (n, not normalised) and plane_color_host are host float[3].
+ * With is_bg [R] and ray_color [R,3] (both or neither) the same launch also does
+ * fill_invalid: ray_color[r, c] += is_bg[r] * bg[r, c].  bg holds bg_cap >= R
+ * rays; R = 0 launches nothing.
+ *
+ * Both take a stream, allocate nothing and read nothing on the host. */
+#define PNR_PLANE_CAM_TILE 64   /* cameras staged in LDS at a time by both kernels */
+int pnr_plane_fg_masks(const float* xyz, int64_t N, const float* cams, int32_t F, int32_t H, int32_t W, uint8_t* fg,
+                       int64_t fg_bytes, void* stream);
+int pnr_plane_bg(const float* campos, const float* raydir, int64_t R, const void* images, int32_t images_u8,
+                 const float* cams, int32_t F, int32_t H, int32_t W, const uint8_t* fg, int64_t fg_bytes,
+                 const float* plane_pnt_host, const float* plane_normal_host, const float* plane_color_host,
+                 float* bg, int64_t bg_cap, const float* is_bg, float* ray_color, void* stream);
 
 /* ------------------------------------------------------------- optimizer */
 /* One Adam step (torch.optim.Adam, amsgrad = False: the optimizer of the

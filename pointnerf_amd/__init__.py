@@ -23,5 +23,6 @@ from .losses import RenderLoss, color_losses, frame_metrics  # noqa: F401
 from .rays import FrameSet, camera_rays  # noqa: F401
 from .seed import seed_points  # noqa: F401
 from .fuse import fuse_depth_maps  # noqa: F401
+from .plane_bg import PlaneBackground  # noqa: F401
 
 __version__ = "0.1.0"

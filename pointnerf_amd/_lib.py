@@ -18,8 +18,9 @@ LIB_PATH = os.environ.get("PNR_LIB", os.path.join(_HERE, "libpnr.so"))
 c_int, c_int8, c_int32, c_int64 = ctypes.c_int, ctypes.c_int8, ctypes.c_int32, ctypes.c_int64
 c_float, c_size_t, c_void_p = ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 PNR_OK, PNR_EINVAL, PNR_EOVERFLOW, PNR_EHIP, PNR_ENOMEM = 0, 1, 2, 3, 4
-ABI_VERSION = 31
+ABI_VERSION = 32
 SEED_CAM_TILE = 64   # PNR_SEED_CAM_TILE (include/pnr.h)
+PLANE_CAM_TILE = 64   # PNR_PLANE_CAM_TILE
 FEAT_H_PITCH = 136   # PNR_FEAT_H_PITCH: uint16 per bf16 feature row (pnr_aggregate_fwd_bf16_hf)
 HEAD_BWD_BLOCKS = 512   # PNR_HEAD_BWD_BLOCKS (include/pnr.h)
 
@@ -361,6 +362,10 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnr_composite_fwd_p": (c_int, [P(QueryParams), P(QueryBufs), P(CompositeParams), c_int64, c_void_p, c_float,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pnr_plane_fg_masks": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
+    "pnr_plane_bg": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32,
+                             c_void_p, c_int64, P(c_float), P(c_float), P(c_float), c_void_p, c_int64, c_void_p,
+                             c_void_p, c_void_p]),
     "pnr_scan_scratch_bytes": (c_int, [c_int64, P(c_size_t)]),
     "pnr_exclusive_scan_i32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_size_t, c_void_p]),
