@@ -85,7 +85,7 @@ extern "C" {
 /* libpnr.so is built with -fvisibility=hidden: only the declarations below are exported. */
 #pragma GCC visibility push(default)
 
-#define PNR_ABI_VERSION 32
+#define PNR_ABI_VERSION 33
 
 enum {
   PNR_OK = 0,
@@ -478,6 +478,22 @@ int pnr_aggregate_fwd_h2(const pnr_points* pts, const pnr_samples* s, const pnr_
  * scale1a / range_flag as pnr_aggregate_fwd_h2. */
 int pnr_point_pre_h2(const pnr_points* pts, const pnr_mlp_h2* wh, void* scratch, size_t scratch_bytes,
                      void* stream);
+/* pnr_aggregate_fwd / _x3 / _h2 with block1.0's point half in a table of the
+ * caller's (ABI 33) instead of at the head of the scratch: p1_table is [n_p1, 256]
+ * fp32, 16-B aligned, n_p1 = n_used with a used list, else n; pts->p1_ready speaks
+ * of this table, and pnr_point_pre_h2 fills it when given it as its scratch.  The
+ * scratch then needs pnr_aggregate_scratch_bytes(n_max, 0) bytes only, so P1
+ * outlives it: the frame render keeps P1 as model state (one build per embedding
+ * and block1.0, not one per frame).  Same kernels, same outputs bit for bit. */
+int pnr_aggregate_fwd_p1(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w, float* p1_table,
+                         float* out_feat, float* out_weight, float* out_conf, void* scratch,
+                         size_t scratch_bytes, void* stream);
+int pnr_aggregate_fwd_x3_p1(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w, const pnr_mlp_x3* wx,
+                            float* p1_table, float* out_feat, float* out_weight, float* out_conf, void* scratch,
+                            size_t scratch_bytes, void* stream);
+int pnr_aggregate_fwd_h2_p1(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w, const pnr_mlp_h2* wh,
+                            float* p1_table, float* out_feat, float* out_weight, float* out_conf, void* scratch,
+                            size_t scratch_bytes, void* stream);
 int pnr_aggregate_fwd_masked(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w,
                              const uint8_t* pair_mask, float* out_feat, float* out_weight,
                              float* out_conf, void* scratch, size_t scratch_bytes, void* stream);

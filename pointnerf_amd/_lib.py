@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PNR_LIB", os.path.join(_HERE, "libpnr.so"))
 c_int, c_int8, c_int32, c_int64 = ctypes.c_int, ctypes.c_int8, ctypes.c_int32, ctypes.c_int64
 c_float, c_size_t, c_void_p = ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 PNR_OK, PNR_EINVAL, PNR_EOVERFLOW, PNR_EHIP, PNR_ENOMEM = 0, 1, 2, 3, 4
-ABI_VERSION = 32
+ABI_VERSION = 33
 SEED_CAM_TILE = 64   # PNR_SEED_CAM_TILE (include/pnr.h)
 PLANE_CAM_TILE = 64   # PNR_PLANE_CAM_TILE
 FEAT_H_PITCH = 136   # PNR_FEAT_H_PITCH: uint16 per bf16 feature row (pnr_aggregate_fwd_bf16_hf)
@@ -206,6 +206,13 @@ SIGNATURES = {
     "pnr_aggregate_fwd_x3": (c_int, [P(Points), P(Samples), P(Mlp), P(MlpX3), c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),
     "pnr_point_pre_h2": (c_int, [P(Points), P(MlpH2), c_void_p, c_size_t, c_void_p]),
+    # the same three with P1 in a table of the caller's, passed behind the packs (ABI 33)
+    "pnr_aggregate_fwd_p1": (c_int, [P(Points), P(Samples), P(Mlp), c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    "pnr_aggregate_fwd_x3_p1": (c_int, [P(Points), P(Samples), P(Mlp), P(MlpX3), c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnr_aggregate_fwd_h2_p1": (c_int, [P(Points), P(Samples), P(Mlp), P(MlpH2), c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnr_aggregate_fwd_h2": (c_int, [P(Points), P(Samples), P(Mlp), P(MlpH2), c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),
     "pnr_aggregate_fwd_masked": (c_int, [P(Points), P(Samples), P(Mlp), c_void_p, c_void_p,

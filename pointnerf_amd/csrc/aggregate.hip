@@ -747,16 +747,19 @@ static size_t scratch_need(int64_t n_max, int64_t n_points) {
 // so its place does not depend on n_max and a later call may reuse it
 // (pnr_points.p1_ready).  Returns the split kernels' tile counter, which stays
 // in the scratch when a training call redirects hid / vmask to the saved arrays.
-static int32_t* carve(AggArgs& a, void* scratch, int64_t n_max, int64_t n_p1) {
+// With a P1 table of the caller's (p1_table) the scratch keeps the layout of
+// n_p1 = 0 (one unused row), so P1 outlives the scratch.
+static int32_t* carve(AggArgs& a, void* scratch, int64_t n_max, int64_t n_p1, float* p1_table) {
   const int64_t nm = hid_rows(n_max);
-  a.p1 = static_cast<float*>(scratch);
-  a.hid = a.p1 + (n_p1 > 0 ? n_p1 : 1) * kHid;
+  if (p1_table) n_p1 = 0;
+  a.p1 = p1_table ? p1_table : static_cast<float*>(scratch);
+  a.hid = static_cast<float*>(scratch) + (n_p1 > 0 ? n_p1 : 1) * kHid;
   a.vmask = reinterpret_cast<int32_t*>(a.hid + nm * kHid);
   return a.vmask + cdiv(nm, 4) * 4;
 }
 
 static int check_common(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w, float* out_feat,
-                        void* scratch, size_t scratch_bytes) {
+                        void* scratch, size_t scratch_bytes, const float* p1_table) {
   PNR_CHECK_ARG(pts && s && w && out_feat, "aggregate: null pointer");
   PNR_CHECK_ARG(pts->xyz && pts->emb, "aggregate: point xyz/emb required");
   PNR_CHECK_ARG(s->sample_w && s->sample_p && s->dirs, "aggregate: sample arrays required");
@@ -776,7 +779,8 @@ static int check_common(const pnr_points* pts, const pnr_samples* s, const pnr_m
   PNR_CHECK_ARG(pts->n > 0, "aggregate: empty point table");
   PNR_CHECK_ARG(!pts->used || (pts->used_map && pts->n_used >= 0 && pts->n_used <= pts->n),
                 "aggregate: used list needs used_map and 0 <= n_used <= n");
-  PNR_CHECK_ARG(scratch_bytes >= scratch_need(s->n_max, pts->used ? pts->n_used : pts->n),
+  PNR_CHECK_ARG(((uintptr_t)p1_table & 15) == 0, "aggregate: p1_table must be 16-B aligned");
+  PNR_CHECK_ARG(scratch_bytes >= scratch_need(s->n_max, p1_table ? 0 : pts->used ? pts->n_used : pts->n),
                 "aggregate: scratch too small (%zu bytes for %lld samples, %lld points)", scratch_bytes,
                 (long long)s->n_max, (long long)pts->n);
   return PNR_OK;
@@ -842,6 +846,7 @@ struct FwdCall {
   const pnr_mlp_h2* wh;         // Arith::H2
   const uint8_t* pair_mask;     // kMasked
   const pnr_agg_saved* saved;   // kTrain
+  float* p1_table;              // the _p1 entry points: P1 lives here, not at the head of the scratch
   bool train() const { return flags & kTrain; }
 };
 
@@ -865,7 +870,7 @@ static int aggregate_forward(const FwdCall& c, const pnr_points* pts, const pnr_
   const bool h2 = c.arith == Arith::H2, guarded = c.flags & kGuarded;
   // ---- every refusal, before the first launch
   PNR_CHECK_ARG(!guarded || (c.wh && c.wh->range_flag), "%s: range_flag required", c.who);
-  if ((rc = check_common(pts, s, w, out_feat, scratch, scratch_bytes))) return rc;
+  if ((rc = check_common(pts, s, w, out_feat, scratch, scratch_bytes, c.p1_table))) return rc;
   if (c.train()) PNR_CHECK_DEFAULT_DIMS(c.who, pts, w);   // the training kernels: E = 32, order 2
   if (c.train() && (rc = check_saved(c.saved))) return rc;
   if (c.flags & kMasked) {
@@ -891,7 +896,7 @@ static int aggregate_forward(const FwdCall& c, const pnr_points* pts, const pnr_
   a.pts = *pts;
   a.s = *s;
   a.w = *w;
-  int32_t* const tile_ctr = carve(a, scratch, s->n_max, pts->used ? pts->n_used : pts->n);
+  int32_t* const tile_ctr = carve(a, scratch, s->n_max, pts->used ? pts->n_used : pts->n, c.p1_table);
   if (c.train()) {   // hid / vmask are kept for the backward
     a.sv = *c.saved;
     a.hid = c.saved->hid;
@@ -997,6 +1002,36 @@ extern "C" int pnr_aggregate_fwd_h2(const pnr_points* pts, const pnr_samples* s,
                                     const pnr_mlp_h2* wh, float* out_feat, float* out_weight, float* out_conf,
                                     void* scratch, size_t scratch_bytes, void* stream) {
   const FwdCall c{"aggregate_h2", Arith::H2, 0, nullptr, wh, nullptr, nullptr};
+  return aggregate_forward(c, pts, s, w, out_feat, out_weight, out_conf, scratch, scratch_bytes, stream);
+}
+
+// The three inference calls with P1 in a table of the caller's (pnr.h, ABI 33).
+static int check_p1_table(const char* who, const float* p1_table) {
+  PNR_CHECK_ARG(p1_table, "%s: null p1_table", who);
+  return PNR_OK;
+}
+
+extern "C" int pnr_aggregate_fwd_p1(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w, float* p1_table,
+                                    float* out_feat, float* out_weight, float* out_conf, void* scratch,
+                                    size_t scratch_bytes, void* stream) {
+  if (int rc = check_p1_table("aggregate_p1", p1_table)) return rc;
+  const FwdCall c{"aggregate_p1", Arith::F32, 0, nullptr, nullptr, nullptr, nullptr, p1_table};
+  return aggregate_forward(c, pts, s, w, out_feat, out_weight, out_conf, scratch, scratch_bytes, stream);
+}
+
+extern "C" int pnr_aggregate_fwd_x3_p1(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w,
+                                       const pnr_mlp_x3* wx, float* p1_table, float* out_feat, float* out_weight,
+                                       float* out_conf, void* scratch, size_t scratch_bytes, void* stream) {
+  if (int rc = check_p1_table("aggregate_x3_p1", p1_table)) return rc;
+  const FwdCall c{"aggregate_x3_p1", Arith::X3, 0, wx, nullptr, nullptr, nullptr, p1_table};
+  return aggregate_forward(c, pts, s, w, out_feat, out_weight, out_conf, scratch, scratch_bytes, stream);
+}
+
+extern "C" int pnr_aggregate_fwd_h2_p1(const pnr_points* pts, const pnr_samples* s, const pnr_mlp* w,
+                                       const pnr_mlp_h2* wh, float* p1_table, float* out_feat, float* out_weight,
+                                       float* out_conf, void* scratch, size_t scratch_bytes, void* stream) {
+  if (int rc = check_p1_table("aggregate_h2_p1", p1_table)) return rc;
+  const FwdCall c{"aggregate_h2_p1", Arith::H2, 0, nullptr, wh, nullptr, nullptr, p1_table};
   return aggregate_forward(c, pts, s, w, out_feat, out_weight, out_conf, scratch, scratch_bytes, stream);
 }
 

@@ -4,6 +4,7 @@ the queue of sync=False calls and the fp32h2 fallback the module's entry points 
 from __future__ import annotations
 
 import gc
+import os
 from collections import namedtuple
 from dataclasses import dataclass
 from typing import Any, NamedTuple
@@ -170,17 +171,20 @@ def with_h2_fallback(model, precision, events, run):
 
 
 class _RenderState:
-    """Device buffers one render stream reuses: the query buffers and the
-    aggregate scratch (whose head holds P1, see pnr_points.p1_ready)."""
+    """Device buffers one render stream reuses: the query buffers, the aggregate scratch and the P1 table
+    (prepared model state like the packs and the grid, valid while p1_key matches)."""
 
     def __init__(self):
+        self.p1 = None              # fp32 paths: P1 table [n_points, 256] (p1_table)
+        self.p1_key = None          # what it was computed from; None: absent
+        self.p1_builds = 0          # P1 builds launched on it (tests, tools)
         self.bufs = None            # launch-stream query buffers (query_chunk)
         self.qring = [None, None]   # query-stream buffer sets, used in turn (query_chunk)
         self.qfree = [None, None]   # per set: event behind its last launch-stream reader (record_chunk)
         self.qslot = 1              # the set the last query-stream query used (query_chunk)
         self.q_xkey = None          # points (storage, version) the query stream last saw (prepare)
         self.scratch, self.scratch_rows = None, 0   # aggregate scratch, the rows it was allocated for (scratch)
-        self.scratch_key = None     # what its P1 was computed from; None: partial or absent (scratch, aggregate_chunk)
+        self.scratch_key = None     # bf16: what the P1 at its head was computed from; None: partial or absent
         self.side = None            # fp32h2: the side stream P1 runs on (start_p1_side)
         self.used_bufs, self.used_n = None, None   # bf16: used_points_buffers for used_n points (aggregate_chunk)
         self.feat = None            # decoded features [rows, 129], reused by every call on this stream (feat_rows)
@@ -219,6 +223,13 @@ _AGGREGATE = {
 }
 
 
+def p1_per_frame() -> bool:
+    """PNR_P1_PER_FRAME=1: every render call builds P1 again unless the caller passes reuse_p1 (what every
+    call did before P1 became model state): the A/B switch of DESIGN §36 and a route test, in the manner of
+    PNR_H2_GENERAL.  Read once per call."""
+    return os.environ.get("PNR_P1_PER_FRAME") == "1"
+
+
 class _RenderCall:
     """One render call.  capacity (every mode but EAGER): valid samples per ray the feature buffer is
     sized for, instead of a host read of each chunk's count; the counts then travel in the record."""
@@ -228,6 +239,7 @@ class _RenderCall:
         self.m, self.mode, self.precision, self.batch, self.state = model, mode, precision, batch, state
         self.force_grid, self.events, self.reuse_p1 = force_grid, events, reuse_p1
         self.capacity, self.qs, self.bf16 = capacity, query_stream, precision == "bf16"
+        self.p1_built, self.p1_per_frame = False, p1_per_frame()
         self.dev, self.R = batch.raydir.device, batch.raydir.shape[0]
         self.chunk = max(1, model.chunk_rays or self.R)   # rays per chunk
         self.n_chunks = max(1, -(-self.R // self.chunk))
@@ -242,7 +254,7 @@ class _RenderCall:
             Sv, feat = self.size_chunk(bufs, r1 - r0)
             e2 = self.mark()
             s = self.samples(bufs, rd, Sv, rc)
-            feat = self.aggregate_chunk(bufs, s, feat, Sv, self.reuse_p1 or r0 > 0, p1_side)
+            feat = self.aggregate_chunk(bufs, s, feat, Sv, p1_side)
             e3 = self.mark()
             self.composite_chunk(bufs, rays, qp, feat, Sv, r0, r1)
             self.record_chunk(ci, bufs)
@@ -285,8 +297,9 @@ class _RenderCall:
         """Outputs, background, camera tables, the precision's packs, the points table, where the counts go."""
         m, b, st, dev = self.m, self.batch, self.state, self.dev
         L.require_gpu(b.raydir)
-        if self.force_grid:
+        if self.force_grid:   # a write the versions did not see: the grid and P1 are both stale
             m.neural_points.querier.grid.key = None
+            st.p1_key = st.scratch_key = None
         self.prepare_outputs()
         if self.qs is not None:
             # the points can change on the launch stream (an optimizer step on xyz, a forced rebuild):
@@ -311,31 +324,35 @@ class _RenderCall:
         self.prepare_tables()
 
     def start_p1_side(self):
-        """fp32h2: block1.0's per-point half (P1) depends on the points and weights only, so it runs on a
+        """fp32h2: block1.0's per-point half (P1) depends on the points and weights only, so it is built
+        once into the state's table (p1_table) and again only when its key changes; a build runs on a
         side stream beside the query (which is latency bound and leaves the MFMA pipes idle) instead of in
-        front of k_pairs_h2; the aggregate waits on the returned event.  Only where the feature buffer,
-        hence the scratch holding P1, is sized before the query, and not under capture (mode.side_p1);
-        and only while P1 is the smaller job: P1 costs ~0.5 us per point, the query ~3.5 us per ray --
+        front of k_pairs_h2, and the aggregate waits on the returned event.  Only in the modes that do not
+        read the counts before the aggregate, and not under capture (mode.side_p1); and only while P1 is
+        the smaller job: P1 costs ~0.5 us per point, the query ~3.5 us per ray --
         measured 0.99 vs 2.25 ms at 2 M points / 640 k rays; at 10 M points / 1.25 M rays the 5.8 ms P1
         outlasted the query and the overlap gained nothing."""
         m, st, dev = self.m, self.state, self.dev
         if not (self.precision == "fp32h2" and self.mode.side_p1 and m.p1_side_stream
                 and self.pts.n <= m.p1_side_max_points_per_ray * self.R):
             return None
-        c0 = min(self.chunk, self.R)
-        Sv0 = min(int(c0 * self.capacity) + 1024, c0 * m.opt.SR)
-        scr0, ready0 = self.scratch(max(Sv0, 1), self.reuse_p1)
+        tab, ready0 = self.p1_table()
         if ready0:
+            # built by an earlier call from these same points and weights: no launch.  The call's "p1"
+            # stage is still recorded, empty: the stage lines of a sync-free fp32h2 call keep their names
+            if self.events is not None:
+                self.events.append(("p1", self.mark(), self.mark()))
             return None
         if st.side is None:
             st.side = torch.cuda.Stream(device=dev)
-        st.side.wait_stream(torch.cuda.current_stream(dev))
+        st.side.wait_stream(torch.cuda.current_stream(dev))   # the launch stream's readers of the old table
         s0 = self.mark(st.side)
-        L.check(L.lib().pnr_point_pre_h2(L.ctypes.byref(self.pts), L.ctypes.byref(self.extra), L.ptr(scr0),
-                                         scr0.numel() * 4, L.c_void_p(st.side.cuda_stream)), "pnr_point_pre_h2")
+        L.check(L.lib().pnr_point_pre_h2(L.ctypes.byref(self.pts), L.ctypes.byref(self.extra), L.ptr(tab),
+                                         tab.numel() * 4, L.c_void_p(st.side.cuda_stream)), "pnr_point_pre_h2")
         s1 = self.mark(st.side)
         ev_p1 = st.side.record_event()
-        scr0.record_stream(st.side)
+        st.p1.record_stream(st.side)
+        self.p1_built_now()
         if self.events is not None:
             self.events.append(("p1", s0, s1))
         return ev_p1
@@ -386,51 +403,89 @@ class _RenderCall:
             self.caps.append((Sv, n_rays))
         return Sv, (self.state.feat_h_rows if self.hf else self.state.feat_rows)(Sv, self.dev)
 
-    def scratch(self, n_max, reuse):
-        """Persistent aggregate scratch (P1 lives at its start, see pnr_points.p1_ready) -> (tensor, P1
-        already valid).  The P1 is valid when reuse is requested and the embedding storage, block1.0 and
-        the precision match the call that wrote it."""
-        st, dev, n_points = self.state, self.dev, self.pts.n
+    def p1_key(self):
+        """What P1 depends on: the precision's kernel, the point count, and the storage and version of the
+        embedding and of block1.0 (an in-place change bumps _version; the grid's contract)."""
         emb = self.m.neural_points.points_embeding
         b1 = self.m.aggregator.block1[0]
         # fp32h2 computes P1 on f16-split MFMA (k_point_pre_h2), the other fp32 paths on fp32 MFMA
-        key = (self.bf16, self.precision == "fp32h2", n_points, emb.data_ptr(), emb._version, b1.weight.data_ptr(),
-               b1.weight._version, b1.bias.data_ptr(), b1.bias._version)
+        return (self.bf16, self.precision == "fp32h2", self.pts.n, emb.data_ptr(), emb._version, b1.weight.data_ptr(),
+                b1.weight._version, b1.bias.data_ptr(), b1.bias._version)
+
+    def p1_fresh(self, key_now):
+        """The P1 a key speaks of may be taken as it is: the key is the call's, and the call is neither one
+        that builds its own (the captured graph, PNR_P1_PER_FRAME=1 without the reuse_p1 hint) nor still
+        before its build."""
+        own = self.mode is CAPTURE or (self.p1_per_frame and not self.reuse_p1)
+        return key_now == self.p1_key() and (self.p1_built or not own)
+
+    def p1_table(self):
+        """The fp32 paths' P1 table -> (the table, P1 already valid).  An allocation of the render
+        state's own, [n_points, 256] (the p1_table of the pnr_aggregate_fwd*_p1 calls), made once per point
+        count and device: the scratch's growth leaves it alone.  Valid while the key it was built from is the call's."""
+        st, dev, n = self.state, self.dev, int(self.pts.n)
+        if st.p1 is None or st.p1.device != dev or st.p1.shape[0] != n:
+            st.p1 = st.p1_key = None   # the old table is freed before the new allocation
+            st.p1 = torch.empty((n, 256), dtype=torch.float32, device=dev)
+        return st.p1, self.p1_fresh(st.p1_key)
+
+    def p1_built_now(self):
+        """A full P1 build into the state's table (bf16: the scratch's start) was just launched."""
+        st = self.state
+        if self.bf16:
+            st.scratch_key = self.p1_key()
+        else:
+            st.p1_key = self.p1_key()
+        self.p1_built = True
+        st.p1_builds += 1
+
+    def scratch(self, n_max):
+        """Persistent aggregate scratch -> (tensor, P1 already valid).  The fp32 paths keep P1 in p1_table;
+        bf16 keeps its bf16 P1 rows at the scratch's start (pnr_points.p1_ready), valid by the same key
+        until the scratch grows."""
+        st, dev = self.state, self.dev
+        n_points = int(self.pts.n) if self.bf16 else 0
         # the one size query that allocates nothing: the persistent scratch is kept while it is large enough
         query = "pnr_aggregate_scratch_bytes_bf16" if self.bf16 else "pnr_aggregate_scratch_bytes"
         nb = L.c_size_t(0)
-        L.check(getattr(L.lib(), query)(int(n_max), int(n_points), L.ctypes.byref(nb)), query)
+        L.check(getattr(L.lib(), query)(int(n_max), n_points, L.ctypes.byref(nb)), query)
         if st.scratch is None or st.scratch.device != dev or st.scratch.numel() * 4 < int(nb.value):
             # headroom (n_max varies per batch) and geometric growth: no allocation per frame
             st.scratch_rows = max(int(n_max * 1.5) + 1024, int(1.5 * st.scratch_rows))
             st.scratch = st.scratch_key = None
-            st.scratch = L.scratch(query, st.scratch_rows, int(n_points), device=dev).view(torch.float32)
-        ready = reuse and st.scratch_key == key
-        st.scratch_key = key
-        return st.scratch, ready
+            st.scratch = L.scratch(query, st.scratch_rows, n_points, device=dev).view(torch.float32)
+        if not self.bf16:
+            st.scratch_key = None   # the scratch's start is this call's hid rows now
+            return st.scratch, self.p1_table()[1]
+        return st.scratch, self.p1_fresh(st.scratch_key)
 
-    def aggregate_chunk(self, bufs, s, feat, Sv, reuse, p1_side):
-        """The precision's aggregate into feat (-> the rows the composite reads), P1 from the scratch if valid."""
+    def aggregate_chunk(self, bufs, s, feat, Sv, p1_side):
+        """The precision's aggregate into feat (-> the rows the composite reads), P1 as it stands if valid."""
         m, st, pts, dev = self.m, self.state, self.pts, self.dev
-        scratch, ready = self.scratch(max(Sv, 1), reuse)
+        scratch, ready = self.scratch(max(Sv, 1))
         # bf16 (config c5: 20 M points, a frame references a fraction of them): block1.0's point half only
         # for the points this batch's neighbour lists reference (pnr_used_points, device list and count),
         # written at their own rows of the P1 table (pnr_points.used without used_map) -- no indirection
         # in the pairs kernel.  (A reuse_p1 call after a used-only one finds the table partial (key
         # cleared): it computes its own used rows, not the whole table.)
-        if self.bf16 and self.mode.used_only and m.p1_used_only and self.n_chunks == 1 and not ready:
+        partial = self.bf16 and self.mode.used_only and m.p1_used_only and self.n_chunks == 1 and not ready
+        if partial:
             if st.used_n != pts.n:
                 st.used_bufs, st.used_n = used_points_buffers(pts.n, dev), pts.n
             pts.used = L.ptr(used_points_device(bufs, m.opt.K, pts.n, st.used_bufs)[0])
             pts.n_used, pts.used_map = pts.n, None
             pts.n_used_dev = bufs.count_ptr(Q.COUNT_N_USED)
-            ready, st.scratch_key = False, None   # the table holds this batch's rows only
-        if p1_side is not None:   # P1 written into this same scratch by the side stream
+            st.scratch_key = None   # the table holds this batch's rows only
+        if p1_side is not None:   # P1 written into the table by the side stream
             torch.cuda.current_stream(dev).wait_event(p1_side)
-            ready = True
+        elif not ready and not partial and Sv > 0:
+            # this launch builds it, in front of the pairs kernel (a call without samples launches nothing)
+            self.p1_built_now()
         pts.p1_ready = int(ready)
-        fn = getattr(L.lib(), self.entry + ("_hf" if self.hf else ""))
+        # the fp32 paths: the entry point's _p1 form, P1 in the state's table behind the packs
+        fn = getattr(L.lib(), self.entry + (("_hf" if self.hf else "") if self.bf16 else "_p1"))
         extra = () if self.extra is None else (L.ctypes.byref(self.extra),)
+        extra += () if self.bf16 else (L.ptr(st.p1),)
         L.check(fn(L.ctypes.byref(pts), L.ctypes.byref(s), L.ctypes.byref(self.mlp), *extra, L.ptr(feat), None, None,
                    L.ptr(scratch), scratch.numel() * 4, L.stream_ptr(dev)), self.entry)
         if self.C == 3:   # upstream colour head: [alpha, rgb] rows
@@ -500,6 +555,7 @@ class _PixelCall(_RenderCall):
         self.m, self.mode, self.precision, self.batch, self.state = model, EAGER, precision, batch, state
         self.force_grid, self.events, self.reuse_p1 = False, events, reuse_p1
         self.capacity, self.qs, self.bf16 = None, None, False
+        self.p1_built, self.p1_per_frame = False, p1_per_frame()
         self.dev, self.R = batch.pixel_idx.device, batch.pixel_idx.shape[0]
         self.chunk = max(1, model.chunk_rays or self.R)
         self.n_chunks = max(1, -(-self.R // self.chunk))

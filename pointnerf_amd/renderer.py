@@ -175,11 +175,17 @@ class NeuralPointsRayMarching(nn.Module):
         Returns ray_color [R,C], opacity [R,SR], is_bg [R], ray_mask [R] (int8).
         ``events``: optional list that receives (stage, start, end) HIP events
         recorded on the launch stream around each stage.
-        ``reuse_p1``: the caller guarantees points_embeding and block1.0 are
-        unchanged since the previous render_rays call (e.g. the other partial
-        frames of one multi-GPU step), so block1.0's per-point half (P1, which
-        does not depend on the camera) is taken from that call's scratch
-        instead of recomputed.  The ray chunks of one call always share it.
+        block1.0's per-point half (P1, which does not depend on the camera)
+        is prepared model state like the weight packs and the grid (DESIGN
+        §36): built by the first call into a table the render state keeps,
+        and again only after points_embeding or block1.0 changed (new storage
+        or an in-place change, which bumps ``_version``), the point count or
+        the precision.  ``reuse_p1`` is kept for its callers and changes
+        nothing (with ``PNR_P1_PER_FRAME=1`` in the environment every call
+        builds P1 again unless it is passed: the behaviour before, for A/B).
+        A write that changes neither storage nor version (through ``.data``,
+        by a raw-pointer kernel) is not seen, exactly as for the grid below:
+        pass ``force_grid=True`` after it, which drops the grid and P1.
         ``ray_cam`` (int32 [R], optional): camera index of each ray into
         campos [n_cams,3] / camrot [n_cams,3,3] -- several frames' rays
         rendered as one batch (``render_views``).
